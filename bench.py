@@ -8,6 +8,12 @@ BASELINE.json configs[1]: model_0, batch 64, 256x256.  Multi-GPU: one process pe
 collective; RCCL is used for the barrier / max-over-ranks timing and the final
 all-gather of per-rank stats.  Rank 0 prints ONE JSON line.
 
+A plain run does only what the headline figure needs: set-up (the shipped tuning replayed),
+preheat, warm-up, the timed steps, the result line.  --full adds, around the same timed steps,
+the per-layer and in-step kernel timing with the roofline figures, the parity probe against
+the oracle, the CPU baseline and the per-rank stats; --dump-outputs DIR writes what the last
+timed step computed.
+
 No PyTorch is imported in this process (torch bundles a second HIP runtime); the
 torch.distributed launcher only provides RANK/LOCAL_RANK/WORLD_SIZE/MASTER_*.
 """
@@ -53,6 +59,15 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure: per-layer and in-step kernel timing with the roofline "
+                         "figures, the reheat they need, the parity probe against the oracle, the CPU "
+                         "baseline, the per-rank device record and the stats all-gather (a plain run only "
+                         "sets up, warms up, times --steps steps and prints the result line)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last step computed (the arrays a caller of "
+                         "the timed path receives) as DIR/<name>.npy in float32, at most 64 MB in all: "
+                         "whole arrays when they fit, else a fixed seeded choice of rows of each")
     ap.add_argument("--model", type=int, default=0)
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--patch", type=int, default=256)
@@ -109,6 +124,30 @@ def parse():
     if args.images is None:
         args.images = 10000 if args.workload == "sharded" else 1
     return args
+
+
+DUMP_BYTES = 60_000_000  # --dump-outputs: float32 payload of all arrays together (below 64 MB with the headers)
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array of `arrays` (name -> ndarray) as out_dir/<name>.npy in
+    float32.  While all of them fit DUMP_BYTES they are written whole, in their own shape;
+    otherwise each gets the share of the budget its size has of the total and keeps that many
+    of its rows (slices along axis 0) — a seeded choice without replacement, in ascending
+    order, the same for the same arguments, so two builds write the same elements."""
+    os.makedirs(out_dir, exist_ok=True)
+    budget = DUMP_BYTES // 4
+    total = sum(a.size for a in arrays.values())
+    for i, (name, a) in enumerate(arrays.items()):
+        if total > budget and a.size:
+            rows = a.reshape(a.shape[0], -1)
+            k = int(budget * a.size // total) // rows.shape[1]
+            if k >= 1:
+                a = rows[np.sort(np.random.default_rng(4321 + i).choice(rows.shape[0], min(k, rows.shape[0]),
+                                                                        replace=False))]
+            else:  # one row alone is over the share: its leading elements
+                a = rows[0, :max(1, int(budget * a.size // total))]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def traffic_path(args, model, lane_b):
@@ -442,49 +481,51 @@ def main():
     if args.pmc_plan:
         return pmc_steady(args, codec, d_in, d_idx, d_rgb, lane_b, M, P)
 
-    # per-layer kernel timing, outside the timed region: HIP events around each launch on
-    # the lane's stream, one lane at the per-launch batch (lane_b), each launch running alone
-    # (exclusive) — the median of --profile-passes passes; it picks the dominant launch group
-    # (the most one-lane time per step) and gives its roofline fraction; the same launches are
-    # also timed in-step (below) and reported beside it
+    # untimed steps first, in every run: the clock the GPU holds under sustained load
     pre = preheat(args, lambda: codec.codec_device(d_in, B, d_idx, d_rgb), codec.synchronize)
-    ms = one_lane_ms(codec, d_in, lane_b, args)
-    # the one-lane profiling is a light load: the clock can drop during it and take a few
-    # hundred steps to come back (two evidence runs of the driver's 20 steps read 7 % slow
-    # after a full preheat: profiles/bench_m0_drv_r05{h,j}.json), so the steady two-lane steps
-    # run again, right before the in-step timing and the timed region
-    pre2 = preheat(args, lambda: codec.codec_device(d_in, B, d_idx, d_rgb), codec.synchronize, args.reheat_s)
-    kernels = codec.layer_kernels(lane_b)
-    groups, rows = kernel_groups(codec, M, P, ms, kernels)
-    names = {lay.name: i for i, lay in enumerate(layer_table(M))}
-    # candidates timed in-step: the four largest by one-lane time per step
-    fams = kernel_families(groups, kernels, names)
-    dom_fam = max(fams, key=lambda f: (fams[f]["ms"], fams[f]["flops"]))
-    cands = list(fams[dom_fam]["members"])
-    cands += [k for k in sorted(groups, key=lambda k: (-groups[k]["ms"], -groups[k]["flops"])) if k not in cands][
-        :max(0, 4 - len(cands))]
-    # the candidates' launches timed in-step, BEFORE the timed region: the same steady two-lane
-    # steps with an event pair per lane around each candidate launch (inside the timed steps the
-    # pairs would cost ≈ 2 %), warm-up steps first to settle the lanes.  Running them here also
-    # brings the GPU to the clock it holds under sustained load: the kernels of a step get
-    # ≈ 7 % faster over the first ≈ 30 steps after the light one-lane profiling (rocprofv3
-    # kernel trace of a 20-step run: step span 411 -> 350 us), which 5 warm-up
-    # steps alone do not cover
-    in_step = {}
-    n_in_step = max(args.in_step_min, min(args.steps, 200))
-    if args.trace_only:  # the same sustained steps, without the event pairs
-        for _ in range(len(cands) * (args.warmup + n_in_step)):
-            codec.codec_device(d_in, B, d_idx, d_rgb)
-    else:
-        for k in cands:
-            codec.set_option("mark_layer", names[groups[k]["layers"][0]])
-            for _ in range(args.warmup):
+    if args.full:
+        # per-layer kernel timing, outside the timed region: HIP events around each launch on
+        # the lane's stream, one lane at the per-launch batch (lane_b), each launch running alone
+        # (exclusive) — the median of --profile-passes passes; it picks the dominant launch group
+        # (the most one-lane time per step) and gives its roofline fraction; the same launches are
+        # also timed in-step (below) and reported beside it
+        ms = one_lane_ms(codec, d_in, lane_b, args)
+        # the one-lane profiling is a light load: the clock can drop during it and take a few
+        # hundred steps to come back (two evidence runs of the driver's 20 steps read 7 % slow
+        # after a full preheat: profiles/bench_m0_drv_r05{h,j}.json), so the steady two-lane steps
+        # run again, right before the in-step timing and the timed region
+        pre2 = preheat(args, lambda: codec.codec_device(d_in, B, d_idx, d_rgb), codec.synchronize, args.reheat_s)
+        kernels = codec.layer_kernels(lane_b)
+        groups, rows = kernel_groups(codec, M, P, ms, kernels)
+        names = {lay.name: i for i, lay in enumerate(layer_table(M))}
+        # candidates timed in-step: the four largest by one-lane time per step
+        fams = kernel_families(groups, kernels, names)
+        dom_fam = max(fams, key=lambda f: (fams[f]["ms"], fams[f]["flops"]))
+        cands = list(fams[dom_fam]["members"])
+        cands += [k for k in sorted(groups, key=lambda k: (-groups[k]["ms"], -groups[k]["flops"]))
+                  if k not in cands][:max(0, 4 - len(cands))]
+        # the candidates' launches timed in-step, BEFORE the timed region: the same steady two-lane
+        # steps with an event pair per lane around each candidate launch (inside the timed steps the
+        # pairs would cost ≈ 2 %), warm-up steps first to settle the lanes.  Running them here also
+        # brings the GPU to the clock it holds under sustained load: the kernels of a step get
+        # ≈ 7 % faster over the first ≈ 30 steps after the light one-lane profiling (rocprofv3
+        # kernel trace of a 20-step run: step span 411 -> 350 us), which 5 warm-up
+        # steps alone do not cover
+        in_step = {}
+        n_in_step = max(args.in_step_min, min(args.steps, 200))
+        if args.trace_only:  # the same sustained steps, without the event pairs
+            for _ in range(len(cands) * (args.warmup + n_in_step)):
                 codec.codec_device(d_in, B, d_idx, d_rgb)
-            codec.mark_durations()
-            for _ in range(n_in_step):
-                codec.codec_device(d_in, B, d_idx, d_rgb)
-            in_step[k] = codec.mark_durations()
-        codec.set_option("mark_layer", -1)
+        else:
+            for k in cands:
+                codec.set_option("mark_layer", names[groups[k]["layers"][0]])
+                for _ in range(args.warmup):
+                    codec.codec_device(d_in, B, d_idx, d_rgb)
+                codec.mark_durations()
+                for _ in range(n_in_step):
+                    codec.codec_device(d_in, B, d_idx, d_rgb)
+                in_step[k] = codec.mark_durations()
+            codec.set_option("mark_layer", -1)
     for _ in range(args.warmup):
         codec.codec_device(d_in, B, d_idx, d_rgb)
     codec.synchronize()
@@ -500,6 +541,49 @@ def main():
     elapsed = time.perf_counter() - t0
     wall1 = time.time()
     t_max = comm.allreduce_max(elapsed)
+    if args.trace_only:
+        if rank == 0:
+            print(json.dumps({"trace_only": True, "ms_per_step": t_max * 1e3 / args.steps,
+                              "launches_per_lane": sum(1 for k in codec.layer_kernels(lane_b) if k)}), flush=True)
+        comm.close()
+        codec.close()
+        return
+    # what the last timed step left in the caller's buffers: symbols and reconstruction
+    rec = d_rgb.download(x.shape, np.uint8)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"symbols": d_idx.download((B, eh, ew, ec), np.uint8),
+                                         "reconstruction": rec})
+    step_ms = t_max * 1e3 / args.steps
+    total_px = world * B * P * P * args.steps
+    value = total_px / t_max / 1e6
+    out = {
+        "metric": "encode+decode MPix/s at 256x256 RGB",
+        "value": round(value, 2),
+        "unit": "MPix/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(step_ms, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic uniform u8 patches (seed 1234+rank), seeded He-normal weights",
+        "config": {"workload": f"model_{M} encode+decode, batch={B} patches of {P}x{P} RGB per GPU",
+                   "model": f"model_{M}", "global_batch": B * world, "patch": P,
+                   "code_shape": [eh, ew, ec], "parallelism": f"image-parallel x{world}"},
+        "lanes": {"streams": args.streams, "patches_per_launch": lane_b, "hip_graph": bool(args.graph)},
+        "host_enqueue_ms_per_step": round(t_enq * 1e3 / args.steps, 4),
+        "preheat": pre,
+        "tuning": tuning,
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        comm.close()
+        codec.close()
+        return
+
     in_step = {k: v for k, v in in_step.items() if len(v)}
     # the dominant launch group: a fixed ranking — the most one-lane (exclusive) GPU time per
     # step (cands[0]).  The in-step ranking is reported beside it but does not choose: with
@@ -511,16 +595,8 @@ def main():
     top_in_step = (max(in_step, key=lambda k: float(np.mean(in_step[k])) * groups[k]["launches"])
                    if in_step else None)
     marks = np.concatenate([in_step[k] for k in members if k in in_step] or [np.zeros(0)])
-    if args.trace_only:
-        if rank == 0:
-            print(json.dumps({"trace_only": True, "ms_per_step": t_max * 1e3 / args.steps,
-                              "launches_per_lane": sum(1 for k in codec.layer_kernels(lane_b) if k)}), flush=True)
-        comm.close()
-        codec.close()
-        return
 
     # per-rank stats -> the one RCCL all-gather (SSE of the last reconstruction)
-    rec = d_rgb.download(x.shape, np.uint8)
     sse = float(np.sum(np.square(rec.astype(np.float64) - x.astype(np.float64))))
     st = dist.RankStats(sse=sse * args.steps, dims=x.size * args.steps, bits=B * eh * ew * ec * args.steps,
                         images=B * args.steps, t_start=wall0, t_end=wall1)
@@ -586,37 +662,15 @@ def main():
             row.update({"ms_per_launch_in_step": round(rmsi, 5), "frac_in_step": ri["frac"]})
         roof_groups.append(row)
 
-    step_ms = t_max * 1e3 / args.steps
-    total_px = world * B * P * P * args.steps
-    value = total_px / t_max / 1e6
-    out = {
-        "metric": "encode+decode MPix/s at 256x256 RGB",
-        "value": round(value, 2),
-        "unit": "MPix/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(step_ms, 4),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic uniform u8 patches (seed 1234+rank), seeded He-normal weights",
-        "config": {"workload": f"model_{M} encode+decode, batch={B} patches of {P}x{P} RGB per GPU",
-                   "model": f"model_{M}", "global_batch": B * world, "patch": P,
-                   "code_shape": [eh, ew, ec], "parallelism": f"image-parallel x{world}"},
+    out.update({
         "roofline": roof,
         "roofline_groups": roof_groups,
         "roofline_step_frac": round(step_roofline(rows, B, step_ms), 4),
-        "lanes": {"streams": args.streams, "patches_per_launch": lane_b, "hip_graph": bool(args.graph)},
-        "host_enqueue_ms_per_step": round(t_enq * 1e3 / args.steps, 4),
-        "preheat": pre,
         "reheat": pre2,
         "ranks": ranks,
-        "tuning": tuning,
         "stats_allgather": {"images": summary["images"], "psnr_db": round(summary["psnr_db"], 3),
                             "raw_bpp": round(summary["bpp"], 4)},
-    }
+    })
     if rank == 0:
         try:
             os.makedirs(os.path.dirname(args.layers_out), exist_ok=True)
@@ -798,9 +852,12 @@ def main_sharded(args):
     t_max = comm.allreduce_max(elapsed)
     st = shard.stats(args.steps, wall0, wall1)
     summary = dist.combine(comm.allgather_stats(st))
-    ranks = rank_devices(comm, codec, rank, local)
-    # the one-lane roofline of the dominant launch group at the shard's batch (as configs[1])
-    ms = one_lane_ms(codec, shard.d_img, lane_b, args) if shard.n >= lane_b else None
+    if args.dump_outputs and rank == 0:  # of rank 0's shard, as the last pass left them
+        dump_outputs(args.dump_outputs, {"symbols": shard.d_sym.download((shard.n, eh, ew, ec), np.uint8),
+                                         "reconstruction": shard.reconstructions()})
+    ranks = rank_devices(comm, codec, rank, local) if args.full else None
+    # --full: the one-lane roofline of the dominant launch group at the shard's batch (as configs[1])
+    ms = one_lane_ms(codec, shard.d_img, lane_b, args) if args.full and shard.n >= lane_b else None
     roof = None
     if ms is not None:
         kernels = codec.layer_kernels(lane_b)
@@ -845,6 +902,8 @@ def main_sharded(args):
         "stats_allgather": {"images": summary["images"], "psnr_db": round(summary["psnr_db"], 3),
                             "raw_bpp": round(summary["bpp"], 4), "per_step_images": summary["images"] // args.steps},
     }
+    if not args.full:
+        del out["roofline"], out["ranks"]
     if rank == 0:
         print(json.dumps(out), flush=True)
     shard.free()
@@ -958,9 +1017,44 @@ def main_image(args):
     wall1 = time.time()
     t_max = comm.allreduce_max(elapsed)
 
+    recs = [d.download(x.shape, np.uint8) for d, x in zip(d_out, imgs)]
+    if args.dump_outputs and rank == 0:  # every image's symbols and filtered reconstruction
+        arrays = {f"symbols_{i}": d.download((npat, eh, ew, ec), np.uint8) for i, d in enumerate(d_sym)}
+        arrays.update({f"reconstruction_{i}": rec for i, rec in enumerate(recs)})
+        dump_outputs(args.dump_outputs, arrays)
+    step_ms = t_max * 1e3 / args.steps
+    value = world * NI * H * W * args.steps / t_max / 1e6
+    out = {
+        "metric": "encode+decode MPix/s at 256x256 RGB",
+        "value": round(value, 2),
+        "unit": "MPix/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(step_ms, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic uniform u8 images (seed 1234+rank), seeded He-normal weights",
+        "config": {"workload": f"model_{M} + rmbe post-filter, {NI} x {W}x{H} RGB image(s) per GPU tiled "
+                               f"{P}x{P} ({npat} patches, {n_win} rmbe windows per image)",
+                   "model": f"model_{M}+rmbe", "images_per_gpu": NI, "image": [H, W], "patch": P,
+                   "code_shape": [eh, ew, ec], "parallelism": f"image-parallel x{world}"},
+        "lanes": {"streams": args.streams, "patches_per_launch": lane_b, "windows_per_launch": win_lane},
+        "tuning": tuning,
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        ic.close()
+        comm.close()
+        post.close()
+        codec.close()
+        return
+
     sse = 0.0
-    for d, x in zip(d_out, imgs):
-        rec = d.download(x.shape, np.uint8)
+    for rec, x in zip(recs, imgs):
         sse += float(np.sum(np.square(rec.astype(np.float64) - x.astype(np.float64))))
     st = dist.RankStats(sse=sse * args.steps, dims=NI * H * W * 3 * args.steps,
                         bits=NI * npat * eh * ew * ec * args.steps, images=NI * args.steps,
@@ -997,33 +1091,13 @@ def main_image(args):
         for x in rr:
             t_min += max(x["flops_per_patch"] * cnt / (PEAK_FP32_TFLOPS * 1e12),
                          (x["bytes_per_patch"] * cnt + x["weight_bytes"]) / (PEAK_HBM_GBS * 1e9))
-    step_ms = t_max * 1e3 / args.steps
-    value = world * NI * H * W * args.steps / t_max / 1e6
-    out = {
-        "metric": "encode+decode MPix/s at 256x256 RGB",
-        "value": round(value, 2),
-        "unit": "MPix/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(step_ms, 4),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": "synthetic uniform u8 images (seed 1234+rank), seeded He-normal weights",
-        "config": {"workload": f"model_{M} + rmbe post-filter, {NI} x {W}x{H} RGB image(s) per GPU tiled "
-                               f"{P}x{P} ({npat} patches, {n_win} rmbe windows per image)",
-                   "model": f"model_{M}+rmbe", "images_per_gpu": NI, "image": [H, W], "patch": P,
-                   "code_shape": [eh, ew, ec], "parallelism": f"image-parallel x{world}"},
+    out.update({
         "roofline": roof,
         "roofline_step_frac": round(t_min * NI * 1e3 / step_ms, 4),
-        "lanes": {"streams": args.streams, "patches_per_launch": lane_b, "windows_per_launch": win_lane},
         "ranks": ranks,
-        "tuning": tuning,
         "stats_allgather": {"images": summary["images"], "psnr_db": round(summary["psnr_db"], 3),
                             "raw_bpp": round(summary["bpp"], 4)},
-    }
+    })
     if rank == 0:
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline_image(M, P, params, SYNTH_MEAN, SYNTH_STD, rparams, H, W,
