@@ -37,6 +37,9 @@ def my_parse_args(argv=None):
     p.add_argument("--raw", action="store_true", help="symbols stored bit-packed (encode.py --raw)")
     p.add_argument("--rmbe", type=str, default="", help="rmbe post-filter weights .npz (submit/2)")
     p.add_argument("--rmbe-norm", type=str, default="rmbe/channel_normalization_params.npz")
+    p.add_argument("--batch-images", type=int, default=1, metavar="N",
+                   help="decode up to N files (at most 512 patches) as one patch batch; same files and "
+                        "output as 1, the default (one image per launch sequence)")
     return p.parse_args(argv)
 
 
@@ -106,9 +109,8 @@ def uncompress(model, args):
     out_dir = args.output_dir.format(args.model_num)
     os.makedirs(out_dir, exist_ok=True)
     t0 = time.time()
-    for filename in sorted(os.listdir(input_dir)):
-        if not filename.endswith(".encoded"):
-            continue
+
+    def read_symbols(filename):
         path = str(Path(input_dir) / filename)
         seq_len, height, width = get_img_info(filename, config)
         if args.raw:
@@ -116,12 +118,29 @@ def uncompress(model, args):
             seq = np.unpackbits(raw)[:seq_len] if Q == 2 else raw[:seq_len]
         else:
             seq = apply_range_decoder(seq_len, path, cum_freq)
-        symbols = seq.astype(np.uint8).reshape(-1, eh, ew, ec)       # decode.py:204-208
-        # decode -> concat_patches -> (rmbe) -> np.around, all on the GPU
-        recons = ic.decode_image(symbols, height, width, post_filter=post is not None)
+        return seq.astype(np.uint8).reshape(-1, eh, ew, ec), height, width   # decode.py:204-208
+
+    def store(filename, recons):
         out_path = get_recons_image_path(filename, args, config)
         print(f"recons_image_path: {out_path}")
         utils.imsave(out_path, recons)
+
+    filenames = [f for f in sorted(os.listdir(input_dir)) if f.endswith(".encoded")]
+    if args.batch_images < 1:
+        raise ValueError("--batch-images must be at least 1")
+    if args.batch_images == 1:
+        for filename in filenames:
+            symbols, height, width = read_symbols(filename)
+            # decode -> concat_patches -> (rmbe) -> np.around, all on the GPU
+            store(filename, ic.decode_image(symbols, height, width, post_filter=post is not None))
+    else:
+        # groups of consecutive files as one patch batch each (ImageCodec.plan_batches)
+        sizes = [get_img_info(f, config)[1:] for f in filenames]
+        for group in ic.plan_batches(sizes, P, args.batch_images):
+            symbols = [read_symbols(filenames[i])[0] for i in group]
+            images = ic.decode_images(symbols, [sizes[i] for i in group], post_filter=post is not None)
+            for i, recons in zip(group, images):
+                store(filenames[i], recons)
     if args.debug_mode == "on":
         print(f"decode time {time.time() - t0:.3f}s")
 

@@ -11,7 +11,8 @@ CUDA_VISIBLE_DEVICES; ``-p`` names the TF checkpoint prefix (read by tf_checkpoi
 (image_codec.py), and all its patches go through the encoder in one call instead of
 ``sess.run`` batches of 64.  Extra optional flags: ``--norm`` (channel statistics
 npz), ``--dist`` (symbol distribution npy), ``--synthetic-weights`` (seeded weights when
-no checkpoint exists), ``--raw`` (store bit-packed symbols, no entropy coding).
+no checkpoint exists), ``--raw`` (store bit-packed symbols, no entropy coding),
+``--batch-images N`` (N > 1: consecutive images share one patch batch, image_codec.py).
 """
 import argparse
 import os
@@ -44,6 +45,9 @@ def my_parse_args(argv=None):
     p.add_argument("--dist", type=str, default="data_info/distribution_info_{}.npy")
     p.add_argument("--synthetic-weights", action="store_true")
     p.add_argument("--raw", action="store_true", help="bit-pack symbols instead of range coding")
+    p.add_argument("--batch-images", type=int, default=1, metavar="N",
+                   help="encode up to N images (at most 512 patches) as one patch batch; same files and "
+                        "output as 1, the default (one image per launch sequence)")
     return p.parse_args(argv)
 
 
@@ -97,9 +101,8 @@ def compress(model, args):
     out_dir = args.output_dir.format(args.model_num)
     os.makedirs(out_dir, exist_ok=True)
     t0 = time.time()
-    for image_path in utils.read_image_list(args.data_list):
-        image = utils.imread(image_path)
-        symbols = ic.encode_image(image)                     # [n, eh, ew, ec] uint8
+
+    def store(image_path, image, symbols):
         shape = symbols.shape[1:]
         seq = symbols.reshape(-1)                            # encode.py:175-182 order
         encodepath = get_encodepath(image_path, image, seq.size, args, config, shape)
@@ -108,6 +111,21 @@ def compress(model, args):
         else:
             apply_range_encoder(seq, encodepath, args, config, cum_freq)
         print(f"encodepath: {encodepath}")
+
+    image_paths = utils.read_image_list(args.data_list)
+    if args.batch_images < 1:
+        raise ValueError("--batch-images must be at least 1")
+    if args.batch_images == 1:
+        for image_path in image_paths:
+            image = utils.imread(image_path)
+            store(image_path, image, ic.encode_image(image))     # [n, eh, ew, ec] uint8
+    else:
+        # groups of consecutive images as one patch batch each (ImageCodec.plan_batches)
+        sizes = [utils.image_size(p) for p in image_paths]
+        for group in ic.plan_batches(sizes, P, args.batch_images):
+            images = [utils.imread(image_paths[i]) for i in group]
+            for i, image, symbols in zip(group, images, ic.encode_images(images)):
+                store(image_paths[i], image, symbols)
     if args.debug_mode == "on":
         print(f"encode time {time.time() - t0:.3f}s")
 

@@ -211,6 +211,37 @@ int tic_patches_to_image_device(tic_handle* h, const float* d_patches, int H, in
  * network of submit/2/rmbe/model.py:113-197 (one handle, no per-call graph rebuild). */
 int tic_rmbe_image_device(tic_handle* h, float* d_img, int H, int W);
 
+/* --- lists of different-sized images as ONE patch batch.  The reference handles images one
+ * after another (encode.py:152 "To be paralleled"); patches are independent, so the images of
+ * a list share one launch sequence.  Image i lies in a device arena at offsets[i], counted in
+ * elements of the arena's type (bytes of the uint8 arena, floats of the float32 arena — the
+ * same array serves both); offsets may have any alignment, any order and gaps.  offsets /
+ * heights / widths are HOST arrays of n_images entries (heights, widths > 0, offsets >= 0),
+ * read during the call only.  Asynchronous on the handle's stream, no host synchronisation.
+ * n_images == 0 does nothing.  tic_encode_device / tic_decode_device / tic_round_u8_device
+ * run on the patch batch / the arena unchanged. --- */
+
+/* tic_image_to_patches_device of every image in one launch: d_patches
+ * [sum_i ceil(H_i/P)*ceil(W_i/P), P, P, 3], the patches of image i behind those of image
+ * i-1, row-major within an image; *n_patches_out receives the sum. */
+int tic_images_to_patches_device(tic_handle* h, const uint8_t* d_images, const int64_t* offsets,
+                                 const int32_t* heights, const int32_t* widths, int n_images, int P,
+                                 uint8_t* d_patches, int* n_patches_out);
+
+/* tic_patches_to_image_device of every image in one launch (the inverse layout, float32,
+ * each image cropped to H_i x W_i).  Arena elements that belong to no image are not written;
+ * TIC_EINVAL when the ranges of two images overlap. */
+int tic_patches_to_images_device(tic_handle* h, const float* d_patches, const int64_t* offsets,
+                                 const int32_t* heights, const int32_t* widths, int n_images, int P,
+                                 float* d_images);
+
+/* tic_rmbe_image_device of every image of a float32 arena, in place: the column-offset windows
+ * of ALL images in one gather, one run of the network and one write-back, then the row-offset
+ * windows likewise (exact: pass 2 of an image depends only on pass 1 of the same image).
+ * TIC_MODEL_RMBE handle; TIC_EINVAL when the ranges of two images overlap. */
+int tic_rmbe_images_device(tic_handle* h, float* d_images, const int64_t* offsets, const int32_t* heights,
+                           const int32_t* widths, int n_images);
+
 /* np.around(x).astype(np.uint8) of n float32 values in [0,255] (half to even; clamped).
  * Replaces: submit/2/decoder.py:176, decode.py:249. */
 int tic_round_u8_device(tic_handle* h, const float* d_in, size_t n, uint8_t* d_out);

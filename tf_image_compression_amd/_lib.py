@@ -64,6 +64,12 @@ SIGNATURES = [
     ("tic_image_to_patches_device", C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp]),
     ("tic_patches_to_image_device", C.c_int, [vp, vp, C.c_int, C.c_int, C.c_int, vp]),
     ("tic_rmbe_image_device", C.c_int, [vp, vp, C.c_int, C.c_int]),
+    ("tic_images_to_patches_device", C.c_int, [vp, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32),
+                                              C.POINTER(C.c_int32), C.c_int, C.c_int, vp, i32p]),
+    ("tic_patches_to_images_device", C.c_int, [vp, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32),
+                                              C.POINTER(C.c_int32), C.c_int, C.c_int, vp]),
+    ("tic_rmbe_images_device", C.c_int, [vp, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32),
+                                        C.POINTER(C.c_int32), C.c_int]),
     ("tic_round_u8_device", C.c_int, [vp, vp, C.c_size_t, vp]),
     ("tic_histogram_device", C.c_int, [vp, vp, C.c_size_t, C.c_int, vp]),
     ("tic_sse_u8_device", C.c_int, [vp, vp, vp, C.c_size_t, vp]),

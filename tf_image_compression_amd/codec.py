@@ -279,6 +279,38 @@ class Codec:
     def rmbe_image_device(self, d_img: DeviceBuffer, H: int, W: int):
         check(lib().tic_rmbe_image_device(self._h, d_img.ptr, H, W), "tic_rmbe_image_device")
 
+    # lists of different-sized images in one arena (tic_image_batch.cpp): ``offsets`` in elements
+    # of the arena's type, ``sizes`` a list of (H, W)
+    @staticmethod
+    def _image_table(offsets, sizes):
+        off = np.ascontiguousarray(offsets, np.int64).reshape(-1)
+        hw = np.asarray(sizes, np.int32).reshape(-1, 2)
+        if off.size != hw.shape[0]:
+            raise ValueError(f"{off.size} offsets for {hw.shape[0]} image sizes")
+        return off, np.ascontiguousarray(hw[:, 0]), np.ascontiguousarray(hw[:, 1])
+
+    def images_to_patches_device(self, d_images: DeviceBuffer, offsets, sizes, P: int,
+                                 d_patches: DeviceBuffer) -> int:
+        """uint8 images of an arena -> one patch batch (tic_images_to_patches_device).  Returns
+        the number of patches."""
+        off, hs, ws = self._image_table(offsets, sizes)
+        n = C.c_int()
+        check(lib().tic_images_to_patches_device(self._h, d_images.ptr, ptr(off, C.c_int64), ptr(hs, C.c_int32),
+                                                 ptr(ws, C.c_int32), off.size, P, d_patches.ptr, C.byref(n)),
+              "tic_images_to_patches_device")
+        return n.value
+
+    def patches_to_images_device(self, d_patches: DeviceBuffer, offsets, sizes, P: int, d_images: DeviceBuffer):
+        off, hs, ws = self._image_table(offsets, sizes)
+        check(lib().tic_patches_to_images_device(self._h, d_patches.ptr, ptr(off, C.c_int64), ptr(hs, C.c_int32),
+                                                 ptr(ws, C.c_int32), off.size, P, d_images.ptr),
+              "tic_patches_to_images_device")
+
+    def rmbe_images_device(self, d_images: DeviceBuffer, offsets, sizes):
+        off, hs, ws = self._image_table(offsets, sizes)
+        check(lib().tic_rmbe_images_device(self._h, d_images.ptr, ptr(off, C.c_int64), ptr(hs, C.c_int32),
+                                           ptr(ws, C.c_int32), off.size), "tic_rmbe_images_device")
+
     def round_u8_device(self, d_in: DeviceBuffer, n: int, d_out: DeviceBuffer):
         check(lib().tic_round_u8_device(self._h, d_in.ptr, n, d_out.ptr), "tic_round_u8_device")
 

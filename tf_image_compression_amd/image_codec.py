@@ -16,6 +16,13 @@ pass that last used the buffer it is about to overwrite (image i-2, a named even
 for everything the rmbe stream has queued.  So the codec of image i+1 runs while the rmbe
 passes of image i do — two streams, two networks, one GPU.  Callers that reuse their own
 output buffer for consecutive images are ordered by the same rule (see decode_image_device).
+
+Lists of images (opt-in; ``encode.py`` / ``decode.py --batch-images N``): the reference takes
+images strictly one after another (encode.py:152, "To be paralleled").  ``encode_images`` /
+``decode_images`` and their ``*_device`` forms put the patches of a whole group of
+different-sized images into ONE patch batch — one tiling launch, one encoder / decoder call,
+one stitch launch, one window batch per rmbe pass (tic_image_batch.cpp) — with the same two
+stitch buffers and the same events as above between groups.  ``plan_batches`` forms the groups.
 """
 from __future__ import annotations
 
@@ -146,6 +153,166 @@ class ImageCodec:
         self.decode_image_device(d_sym, H, W, d_out, post_filter)
         self.synchronize()
         return d_out.download((H, W, 3), np.uint8)
+
+    # ------------------------------------------------------------------ lists of images
+    # Several images of different sizes as ONE patch batch (tic_image_batch.cpp): an image of
+    # 384-2048 px is 4-64 patches at P = 256, so one image per launch sequence runs the conv
+    # kernels far below the batch they are tuned at.  The images of a group lie in one device
+    # arena, image i at ``offsets[i]`` — bytes of the uint8 arenas, floats of the float32
+    # stitch arena, the same list for both.
+    @staticmethod
+    def plan_batches(sizes, P: int, max_images: int, max_patches: int = 512) -> list[list[int]]:
+        """Consecutive groups of image indices, in list order: a group closes when the next
+        image would take it past ``max_images`` images or ``max_patches`` patches; an image
+        that alone exceeds ``max_patches`` forms its own group.  (512 patches of 256x256x3
+        float32 are a 403 MB patch buffer.)  Pure host arithmetic, no device."""
+        if max_images < 1 or max_patches < 1:
+            raise ValueError("max_images and max_patches must be positive")
+        groups: list[list[int]] = []
+        cur: list[int] = []
+        used = 0
+        for i, (H, W) in enumerate(sizes):
+            n = -(-int(H) // P) * -(-int(W) // P)
+            if cur and (len(cur) >= max_images or used + n > max_patches):
+                groups.append(cur)
+                cur, used = [], 0
+            cur.append(i)
+            used += n
+        if cur:
+            groups.append(cur)
+        return groups
+
+    @staticmethod
+    def packed_offsets(sizes) -> tuple[list[int], int]:
+        """Offsets of images laid back to back, and the arena's length (elements)."""
+        offs, end = [], 0
+        for H, W in sizes:
+            offs.append(end)
+            end += int(H) * int(W) * 3
+        return offs, end
+
+    def _num_patches_list(self, sizes) -> int:
+        return sum(self.num_patches(int(H), int(W)) for H, W in sizes)
+
+    @staticmethod
+    def _runs(offsets, sizes):
+        """The images' element ranges merged into maximal contiguous runs [(start, length)]."""
+        spans = sorted((int(o), int(o) + int(H) * int(W) * 3) for o, (H, W) in zip(offsets, sizes))
+        runs: list[list[int]] = []
+        for lo, hi in spans:
+            if runs and lo == runs[-1][1]:
+                runs[-1][1] = hi
+            else:
+                runs.append([lo, hi])
+        return [(lo, hi - lo) for lo, hi in runs]
+
+    def encode_images_device(self, d_images: DeviceBuffer, offsets, sizes, d_sym: DeviceBuffer) -> int:
+        """uint8 HWC images of one arena (device) -> symbols [n, eh, ew, ec] (device), the
+        patches of image i behind those of image i-1.  Returns n."""
+        P = self.codec.patch_size
+        n = self._num_patches_list(sizes)
+        if n == 0:
+            return 0
+        d_pat = self._buf("patches_u8", n * P * P * 3)
+        got = self.codec.images_to_patches_device(d_images, offsets, sizes, P, d_pat)
+        assert got == n, (got, n)
+        self.codec.encode_device(d_pat, n, d_sym)
+        return n
+
+    def decode_images_device(self, d_sym: DeviceBuffer, offsets, sizes, d_out: DeviceBuffer,
+                             post_filter: bool = True) -> None:
+        """symbols of a group (device) -> uint8 HWC images in the arena ``d_out`` (device),
+        image i at byte ``offsets[i]``; bytes of ``d_out`` that belong to no image are not
+        written.  One decoder call, one stitch launch and (with the post-filter) one gather /
+        network run / write-back per rmbe pass for the whole group.  Readiness of ``d_out``
+        and the hand-off between the codec's and the post-filter's stream are those of
+        ``decode_image_device``: the stitch arena alternates between the same two buffers, the
+        codec overwrites one only after the rmbe pass that last read it, and nothing here
+        synchronises with the host, so groups can be enqueued back to back."""
+        P = self.codec.patch_size
+        n = self._num_patches_list(sizes)
+        if n == 0:
+            return
+        extent = max(int(o) + int(H) * int(W) * 3 for o, (H, W) in zip(offsets, sizes))
+        runs = self._runs(offsets, sizes)
+        d_f = self._buf("patches_f32", n * P * P * 3 * 4)
+        if post_filter and self.post is not None:
+            k = self._slot
+            self._slot = (k + 1) % self.NSLOT
+            self.last_slot = k
+            d_img = self._buf(f"image_f32_{k}", extent * 4)
+            self.codec.decode_device(d_sym, n, None, d_f)
+            self.codec.wait_event(self.post, k)
+            self.codec.patches_to_images_device(d_f, offsets, sizes, P, d_img)
+            self.codec.record(k)
+            self.post.wait_event(self.codec, k)
+            self.post.rmbe_images_device(d_img, offsets, sizes)
+            for lo, ln in runs:
+                self.post.round_u8_device(d_img.view(lo * 4), ln, d_out.view(lo))
+            self.post.record(k)
+        else:
+            d_img = self._buf("image_f32_0", extent * 4)
+            if self.post is not None:
+                self.codec.wait_event(self.post, 0)
+            self.codec.decode_device(d_sym, n, None, d_f)
+            self.codec.patches_to_images_device(d_f, offsets, sizes, P, d_img)
+            for lo, ln in runs:
+                self.codec.round_u8_device(d_img.view(lo * 4), ln, d_out.view(lo))
+            if self.post is not None:
+                self.codec.record(0)
+                self.post.wait_event(self.codec, 0)
+
+    def encode_images(self, images) -> list[np.ndarray]:
+        """[uint8 [H_i, W_i, 3]] -> [uint8 symbols [n_i, eh, ew, ec]]: ``encode_image`` of every
+        image, as one upload, one patch batch and one download."""
+        imgs = [np.ascontiguousarray(im) for im in images]
+        for im in imgs:
+            if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3 or im.size == 0:
+                raise ValueError(f"image must be uint8 [H, W, 3], got {im.dtype} {im.shape}")
+        if not imgs:
+            return []
+        sizes = [im.shape[:2] for im in imgs]
+        offsets, total = self.packed_offsets(sizes)
+        eh, ew, ec = self.codec.code_shape
+        counts = [self.num_patches(H, W) for H, W in sizes]
+        n = sum(counts)
+        d_img = self._buf("image_u8", total)
+        d_img.upload(np.concatenate([im.reshape(-1) for im in imgs]))
+        d_sym = self._buf("symbols", n * eh * ew * ec)
+        self.encode_images_device(d_img, offsets, sizes, d_sym)
+        sym = d_sym.download((n, eh, ew, ec), np.uint8)
+        cuts = np.cumsum(counts)[:-1]
+        return [np.ascontiguousarray(s) for s in np.split(sym, cuts)]
+
+    def decode_images(self, symbols_list, sizes, post_filter: bool = True) -> list[np.ndarray]:
+        """[uint8 symbols [n_i, eh, ew, ec]], [(H_i, W_i)] -> [uint8 [H_i, W_i, 3]]:
+        ``decode_image`` of every image, as one upload, one patch batch and one download."""
+        eh, ew, ec = self.codec.code_shape
+        sizes = [(int(H), int(W)) for H, W in sizes]
+        if len(symbols_list) != len(sizes):
+            raise ValueError(f"{len(symbols_list)} symbol arrays for {len(sizes)} image sizes")
+        if not sizes:
+            return []
+        parts = []
+        for s, (H, W) in zip(symbols_list, sizes):
+            if H <= 0 or W <= 0:
+                raise ValueError(f"image size {H}x{W} must be positive")
+            s = np.ascontiguousarray(s, np.uint8).reshape(-1, eh, ew, ec)
+            if s.shape[0] != self.num_patches(H, W):
+                raise ValueError(f"{s.shape[0]} patches of symbols for a {H}x{W} image "
+                                 f"(expected {self.num_patches(H, W)})")
+            if s.size and int(s.max()) >= self.codec.quan_scale:
+                raise ValueError("symbols out of range [0, quan_scale)")
+            parts.append(s)
+        sym = np.concatenate(parts)
+        offsets, total = self.packed_offsets(sizes)
+        d_sym = self._buf("symbols", sym.nbytes)
+        d_sym.upload(sym)
+        d_out = self._buf("image_out", total)
+        self.decode_images_device(d_sym, offsets, sizes, d_out, post_filter)
+        self.synchronize()
+        flat = d_out.download((total,), np.uint8)
+        return [flat[o:o + H * W * 3].reshape(H, W, 3).copy() for o, (H, W) in zip(offsets, sizes)]
 
     def close(self) -> None:
         for b in self._bufs.values():

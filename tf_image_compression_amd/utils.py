@@ -62,6 +62,14 @@ def imread(path):
     return img
 
 
+def image_size(path):
+    """(height, width) from the file's header, without decoding the pixels."""
+    from PIL import Image
+    with Image.open(path) as im:
+        w, h = im.size
+    return h, w
+
+
 def imsave(path, image):
     from PIL import Image
     Image.fromarray(np.asarray(image, dtype=np.uint8)).save(path)
