@@ -7,7 +7,7 @@ BUILD    := build
 LIB      := tf_image_compression_amd/libtic.so
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -Iinclude -I$(CSRC)
 KERNELS  := conv_s1 conv_s2 conv_t2 conv_rgb conv_chain image_ops
-OBJS     := $(addprefix $(BUILD)/,$(addsuffix .o,$(KERNELS))) $(BUILD)/tic_image_batch.o $(BUILD)/range_coder.o \
+OBJS     := $(addprefix $(BUILD)/,$(addsuffix .o,$(KERNELS))) $(BUILD)/tic_msssim.o $(BUILD)/range_coder.o \
             $(BUILD)/host_util.o
 HDRS     := $(wildcard $(CSRC)/*.h) include/tic.h
 
@@ -16,10 +16,10 @@ all: $(LIB)
 $(BUILD)/%.o: $(CSRC)/%.hip $(HDRS) | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-# tic_image_batch.cpp includes tic_runtime.cpp: the host runtime and the image-list entries
-# are one translation unit (the entries use the handle's internals; tic_runtime.cpp itself
-# stays as the shipped tuning states were stamped)
-$(BUILD)/tic_image_batch.o: $(CSRC)/tic_image_batch.cpp $(CSRC)/tic_runtime.cpp $(HDRS) | $(BUILD)
+# tic_msssim.cpp includes tic_image_batch.cpp, which includes tic_runtime.cpp: the host runtime,
+# the image-list entries and the MS-SSIM entries are one translation unit (the entries use the
+# handle's internals; tic_runtime.cpp itself stays as the shipped tuning states were stamped)
+$(BUILD)/tic_msssim.o: $(CSRC)/tic_msssim.cpp $(CSRC)/tic_image_batch.cpp $(CSRC)/tic_runtime.cpp $(HDRS) | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
 
 $(BUILD)/range_coder.o: $(CSRC)/range_coder.cpp include/tic.h | $(BUILD)

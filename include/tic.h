@@ -257,6 +257,33 @@ int tic_histogram_device(tic_handle* h, const uint8_t* d_sym, size_t n, int Q, u
  * (processing_utils/evaluate.py:10-32; dataset PSNR = 10 log10(255^2 sum(dims)/sum(SSE))). */
 int tic_sse_u8_device(tic_handle* h, const uint8_t* d_a, const uint8_t* d_b, size_t n, uint64_t* d_acc);
 
+/* --- MS-SSIM (Wang et al. 2003 with the choices of tf.image.ssim_multiscale: 11-tap Gaussian
+ * window of sigma 1.5, "valid" filtering, C1 = (0.01*255)^2, C2 = (0.03*255)^2, five scales, each
+ * the 2x2 mean of the one before with an odd last row / column paired with itself) of lists of
+ * uint8 HWC image pairs.  Replaces: nothing in the reference's own code — processing_utils/
+ * evaluate.py:10-32 has the PSNR only, while the CLIC challenge the codec was built for
+ * (submit/) ranks by PSNR and MS-SSIM, computed by the organisers' host script. --- */
+
+/* Bytes of device scratch tic_msssim_images_device needs for images of these sizes (pyramid
+ * planes and per-workgroup partial sums).  Host arithmetic: no device, no handle.  TIC_EINVAL
+ * for a null pointer, a negative count or a side below 161 (161 -> 81 -> 41 -> 21 -> 11). */
+int tic_msssim_scratch_bytes(const int32_t* heights, const int32_t* widths, int n_images, size_t* bytes);
+
+/* Image i of both uint8 arenas lies at byte offsets[i] (any alignment, order, gaps; HOST arrays
+ * as for the image-list entries above).  d_out: double [n_images][5][3][2], fully overwritten:
+ * [j][c][0] = sum of cs, [j][c][1] = sum of l*cs over the (h_j-10)(w_j-10) valid positions of
+ * scale j and channel c (per-position values float32, sums float64); the host forms
+ * prod_j max(mean cs_j, 0)^w_j * max(mean ssim_4, 0)^w_4 per channel and averages the channels.
+ * Asynchronous on the handle's stream, no host synchronisation, any list length; d_scratch
+ * (8-byte aligned, caller-owned) is only used during the call's kernels.  Deterministic (no
+ * floating-point atomics): the 30 doubles of an image are bit-identical from call to call and do
+ * not depend on the other images, on its position in the list or on its offset.  TIC_EINVAL with
+ * nothing launched for a null handle / pointer, a side below 161, a negative count or a scratch
+ * that is too small; n_images == 0 does nothing. */
+int tic_msssim_images_device(tic_handle* h, const uint8_t* d_a, const uint8_t* d_b, const int64_t* offsets,
+                             const int32_t* heights, const int32_t* widths, int n_images, void* d_scratch,
+                             size_t scratch_bytes, double* d_out);
+
 /* hipMemsetAsync on the handle's stream. */
 int tic_memset_device(tic_handle* h, void* d_ptr, int value, size_t bytes);
 

@@ -70,6 +70,10 @@ SIGNATURES = [
                                               C.POINTER(C.c_int32), C.c_int, C.c_int, vp]),
     ("tic_rmbe_images_device", C.c_int, [vp, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32),
                                         C.POINTER(C.c_int32), C.c_int]),
+    ("tic_msssim_scratch_bytes", C.c_int, [C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int,
+                                          C.POINTER(C.c_size_t)]),
+    ("tic_msssim_images_device", C.c_int, [vp, vp, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int32),
+                                          C.POINTER(C.c_int32), C.c_int, vp, C.c_size_t, vp]),
     ("tic_round_u8_device", C.c_int, [vp, vp, C.c_size_t, vp]),
     ("tic_histogram_device", C.c_int, [vp, vp, C.c_size_t, C.c_int, vp]),
     ("tic_sse_u8_device", C.c_int, [vp, vp, vp, C.c_size_t, vp]),

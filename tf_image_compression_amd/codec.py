@@ -311,6 +311,32 @@ class Codec:
         check(lib().tic_rmbe_images_device(self._h, d_images.ptr, ptr(off, C.c_int64), ptr(hs, C.c_int32),
                                            ptr(ws, C.c_int32), off.size), "tic_rmbe_images_device")
 
+    # MS-SSIM of lists of uint8 image pairs (tic_msssim.cpp)
+    @staticmethod
+    def msssim_scratch_bytes(sizes) -> int:
+        """Bytes of device scratch ``msssim_images_device`` needs for images of these (H, W)
+        (tic_msssim_scratch_bytes: host arithmetic, no device)."""
+        hw = np.asarray(sizes, np.int32).reshape(-1, 2)
+        hs, ws = np.ascontiguousarray(hw[:, 0]), np.ascontiguousarray(hw[:, 1])
+        if hw.shape[0] == 0:  # an empty array has no address to pass
+            hs = ws = np.zeros(1, np.int32)
+        n = C.c_size_t()
+        check(lib().tic_msssim_scratch_bytes(ptr(hs, C.c_int32), ptr(ws, C.c_int32), hw.shape[0], C.byref(n)),
+              "tic_msssim_scratch_bytes")
+        return n.value
+
+    def msssim_images_device(self, d_a: DeviceBuffer, d_b: DeviceBuffer, offsets, sizes, d_scratch: DeviceBuffer,
+                             d_out: DeviceBuffer) -> None:
+        """Sums of cs and l*cs per scale and channel of every image pair of two uint8 arenas
+        (image i of both at byte ``offsets[i]``) into ``d_out``: float64 [n, 5, 3, 2]
+        (tic_msssim_images_device; evaluate.msssim_from_sums combines them)."""
+        off, hs, ws = self._image_table(offsets, sizes)
+        if d_out.nbytes < off.size * 30 * 8:
+            raise ValueError(f"d_out holds {d_out.nbytes} bytes, {off.size} images need {off.size * 30 * 8}")
+        check(lib().tic_msssim_images_device(self._h, d_a.ptr, d_b.ptr, ptr(off, C.c_int64), ptr(hs, C.c_int32),
+                                             ptr(ws, C.c_int32), off.size, d_scratch.ptr, d_scratch.nbytes,
+                                             d_out.ptr), "tic_msssim_images_device")
+
     def round_u8_device(self, d_in: DeviceBuffer, n: int, d_out: DeviceBuffer):
         check(lib().tic_round_u8_device(self._h, d_in.ptr, n, d_out.ptr), "tic_round_u8_device")
 

@@ -314,6 +314,74 @@ class ImageCodec:
         flat = d_out.download((total,), np.uint8)
         return [flat[o:o + H * W * 3].reshape(H, W, 3).copy() for o, (H, W) in zip(offsets, sizes)]
 
+    # ------------------------------------------------------------------ rate / distortion
+    def evaluate_images(self, images, post_filter: bool = True, cum_freq=None) -> list[dict]:
+        """Round trip of a list of uint8 [H_i, W_i, 3] images with its quality and rate measures,
+        without leaving the device: one upload, ``encode_images_device`` / ``decode_images_device``
+        on one arena, per image the exact squared error (tic_sse_u8_device) and the symbol
+        histogram (tic_histogram_device) through views, one tic_msssim_images_device call over
+        the images with both sides >= 161 (smaller ones get ``msssim = nan``), one download of
+        the small results.  Per image: ``sse`` (int), ``psnr`` (evaluate.mse2psnr of sse / dims),
+        ``msssim``, ``counts`` (uint64 [Q]), ``n_symbols`` and ``est_bits``
+        (evaluate.estimated_bits under ``cum_freq``, a range_coder.symbol_table table; None
+        without one).  Images start at 4-byte boundaries of the arena (the alignment
+        tic_sse_u8_device asks for)."""
+        from . import evaluate as ev
+        imgs = [np.ascontiguousarray(im) for im in images]
+        for im in imgs:
+            if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3 or im.size == 0:
+                raise ValueError(f"image must be uint8 [H, W, 3], got {im.dtype} {im.shape}")
+        if not imgs:
+            return []
+        c = self.codec
+        Q = c.quan_scale
+        sizes = [tuple(int(v) for v in im.shape[:2]) for im in imgs]
+        offsets, total = [], 0
+        for H, W in sizes:
+            offsets.append(total)
+            total += -(-(H * W * 3) // 4) * 4
+        code = int(np.prod(c.code_shape))
+        if code % 4:
+            raise ValueError(f"code of {code} symbols per patch: the per-image histogram needs a multiple of 4")
+        counts = [self.num_patches(H, W) for H, W in sizes]
+        pbase = np.concatenate([[0], np.cumsum(counts)])
+        arena = np.zeros(total, np.uint8)
+        for im, off in zip(imgs, offsets):
+            arena[off:off + im.size] = im.reshape(-1)
+        d_img = self._buf("image_u8", total)
+        d_img.upload(arena)
+        d_sym = self._buf("symbols", int(pbase[-1]) * code)
+        d_out = self._buf("image_out", total)
+        self.encode_images_device(d_img, offsets, sizes, d_sym)
+        self.decode_images_device(d_sym, offsets, sizes, d_out, post_filter)
+        if post_filter and self.post is not None:
+            c.wait_event(self.post, self.last_slot)  # d_out was written on the post-filter's stream
+        big = [i for i, (H, W) in enumerate(sizes) if min(H, W) >= ev.MSSSIM_MIN_SIDE]
+        n, rec = len(imgs), (1 + Q) * 8  # per image: sse, counts[Q] (uint64); then 30 doubles per MS-SSIM image
+        d_res = self._buf("eval_results", n * rec + len(big) * 240)
+        c.memset_device(d_res, 0, n * rec)
+        for i, (H, W) in enumerate(sizes):
+            c.sse_u8_device(d_img.view(offsets[i]), d_out.view(offsets[i]), H * W * 3, d_res.view(i * rec))
+            c.histogram_device(d_sym.view(int(pbase[i]) * code), counts[i] * code, Q, d_res.view(i * rec + 8))
+        if big:
+            bsizes = [sizes[i] for i in big]
+            d_scr = self._buf("msssim_scratch", c.msssim_scratch_bytes(bsizes))
+            c.msssim_images_device(d_img, d_out, [offsets[i] for i in big], bsizes, d_scr, d_res.view(n * rec))
+        raw = d_res.download((n * rec + len(big) * 240,), np.uint8)
+        ints = raw[:n * rec].view(np.uint64).reshape(n, 1 + Q)
+        sums = raw[n * rec:].view(np.float64).reshape(len(big), 5, 3, 2)
+        ms = {i: ev.msssim_from_sums(sums[k], *sizes[i]) for k, i in enumerate(big)}
+        out = []
+        for i, (H, W) in enumerate(sizes):
+            sse = int(ints[i, 0])
+            cnt = ints[i, 1:].copy()
+            with np.errstate(divide="ignore"):
+                psnr = float(ev.mse2psnr(np.float64(sse) / (H * W * 3)))
+            out.append({"sse": sse, "psnr": psnr, "msssim": ms.get(i, float("nan")), "counts": cnt,
+                        "n_symbols": counts[i] * code,
+                        "est_bits": None if cum_freq is None else ev.estimated_bits(cnt, cum_freq)})
+        return out
+
     def close(self) -> None:
         for b in self._bufs.values():
             b.free()
