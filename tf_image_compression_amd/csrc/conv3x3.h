@@ -711,7 +711,9 @@ __global__ void __launch_bounds__(256) convT_rgb_scatter_kernel(const RgbOutArgs
 // 39 KB instead of 64 KB
 // at TH1 = 4, four workgroups per CU instead of two.  Bit-identical to the padded form.
 // ---------------------------------------------------------------------------------------
-template <int C0, int C1, int TH1, bool U8, bool CMP = false>
+// TS: the phase timestamps (TIC_ENC01_TIMING) compiled in — the product instances carry neither
+// their branches nor the scheduling fences they are.
+template <int C0, int C1, int TH1, bool U8, bool CMP = false, bool TS = false>
 __global__ void __launch_bounds__(256, CMP ? (TH1 >= 8 ? 2 : 4) : 1) enc01_kernel(const Enc01Args a) {
   static_assert(C0 % 16 == 0 && C1 % 16 == 0 && (TH1 % 4 == 0 || TH1 == 2), "tile");
   constexpr int R0 = 4 * TH1 + 3;        // RGB rows
@@ -758,9 +760,10 @@ __global__ void __launch_bounds__(256, CMP ? (TH1 >= 8 ? 2 : 4) : 1) enc01_kerne
   const int gx0 = blockIdx.x * 16, gy0 = blockIdx.y * TH1, nimg = blockIdx.z;
   // timing probe: s_memrealtime (100 MHz) by thread 0 at the phase boundaries
   auto stamp = [&](int k) {
-    if (a.tstamp && tid == 0)
-      a.tstamp[((size_t)(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 8 + k] =
-          __builtin_amdgcn_s_memrealtime();
+    if constexpr (TS)
+      if (a.tstamp && tid == 0)
+        a.tstamp[((size_t)(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 8 + k] =
+            __builtin_amdgcn_s_memrealtime();
   };
   stamp(0);
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -789,9 +792,15 @@ __global__ void __launch_bounds__(256, CMP ? (TH1 >= 8 ? 2 : 4) : 1) enc01_kerne
     rgb[c * RGBP + rr * RP4 + (col & 3) * QJ + (col >> 2)] = __fdiv_rn(__fsub_rn(x, a.mean[c]), a.std[c]);
   };
   // zero the planes first where the tile leaves the image (SAME padding)
-  const bool edge = iy0 < 0 || ix0 < 0 || iy0 + R0 > a.H || ix0 + 68 > a.W || !U8 || (ix0 * 3) % 4 != 0;
-  // interior u8 tiles: each thread unpacks 4-pixel groups (12 bytes) of the 68-pixel row
-  // segments; their loads are issued first so they fly together with the table's
+  const bool border = iy0 < 0 || ix0 < 0 || iy0 + R0 > a.H || ix0 + 68 > a.W;
+  // u8 tiles that start inside the image: each thread unpacks 4-pixel groups (12 bytes) of the
+  // 68-pixel row segments; their loads are issued first so they fly together with the table's.
+  // A tile that leaves the image below or to the right takes this path too where every group
+  // lies wholly inside or wholly outside (W and ix0 multiples of 4) — at 256 x 256 that is the
+  // last tile row and column, 19 of 64 tiles; the groups outside keep the planes' zeros.  The
+  // rest (f32 input, tiles above / left of the image, odd alignments) go pixel by pixel.
+  const bool edge = !U8 || iy0 < 0 || ix0 < 0 || (ix0 * 3) % 4 != 0 || (border && (a.W % 4 != 0 || ix0 % 4 != 0));
+  const bool zfill = edge || border;
   constexpr int GPR = 17, NG = R0 * GPR, NGI = (NG + 255) / 256;
   // the table's loads go out first (L2-resident): with in-order load returns, its LDS copy
   // then waits only for them, not for the u8 rows behind them
@@ -801,15 +810,18 @@ __global__ void __launch_bounds__(256, CMP ? (TH1 >= 8 ? 2 : 4) : 1) enc01_kerne
     for (int i = 0; i < 3; ++i) lutv[i] = a.nlut[i * 256 + tid];
   }
   uint32_t wpre[NGI][3];
+  bool gin[NGI];  // the group lies inside the image
   if constexpr (U8) {
     if (!edge) {
 #pragma unroll
       for (int i = 0; i < NGI; ++i) {
         const int e = i * 256 + tid;
-        if (e < NG) {
-          const int rr = e / GPR, g = e % GPR;
+        const int rr = e / GPR, g = e % GPR;
+        gin[i] = e < NG && (!border || (iy0 + rr < a.H && ix0 + 4 * g < a.W));
+        if (gin[i]) {
           const uint32_t* src = reinterpret_cast<const uint32_t*>(
-              reinterpret_cast<const uint8_t*>(a.in) + ((size_t)(nimg * a.H + iy0 + rr) * a.W + ix0) * 3 + 12 * g);
+              reinterpret_cast<const uint8_t*>(a.in) + ((size_t)(nimg * a.H + iy0) * a.W + ix0) * 3 +
+              (unsigned)(rr * a.W * 3 + 12 * g));
           wpre[i][0] = src[0];
           wpre[i][1] = src[1];
           wpre[i][2] = src[2];
@@ -817,13 +829,13 @@ __global__ void __launch_bounds__(256, CMP ? (TH1 >= 8 ? 2 : 4) : 1) enc01_kerne
       }
     }
   }
-  if (edge)
+  if (zfill)
     for (int e = tid; e < 3 * RGBP; e += 256) rgb[e] = 0.f;
   if constexpr (U8) {  // the host's f32 table (tic_finalize), same values as (v - mean) / std here
 #pragma unroll
     for (int i = 0; i < 3; ++i) lut[i * 256 + tid] = lutv[i];
   }
-  if (edge || U8) __syncthreads();
+  if (zfill || U8) __syncthreads();
   stamp(1);
   if constexpr (U8) {
     if (!edge) {
@@ -831,7 +843,7 @@ __global__ void __launch_bounds__(256, CMP ? (TH1 >= 8 ? 2 : 4) : 1) enc01_kerne
 #pragma unroll
       for (int i = 0; i < NGI; ++i) {
         const int e = i * 256 + tid;
-        if (e >= NG) break;
+        if (!gin[i]) continue;
         const int rr = e / GPR, g = e % GPR;
         float* const dst = rgb + rr * RP4 + g;
 #pragma unroll
@@ -1023,13 +1035,30 @@ __global__ void __launch_bounds__(256, CMP ? (TH1 >= 8 ? 2 : 4) : 1) enc01_kerne
   for (int mb = 0; mb < MB; ++mb)
 #pragma unroll
     for (int nb = 0; nb < NB1; ++nb) acc[mb][nb] = f32x4{0.f, 0.f, 0.f, 0.f};
+  // Compact form with a key per slot (GRP == 1): slot = u + li + the step's constant, u the
+  // wave's first tile row.  The lane's byte offset with the key of each residue of the constant
+  // mod NCH is formed once (xb; the residues no step uses are never computed); a step then adds
+  // its constant as the read's immediate and flips the chunk's high bits by one xor.
+  constexpr bool KEYED = CMP && GRP == 1 && KC1 <= 2;
+  int xb[KEYED ? NCH : 1];
+  if constexpr (KEYED) {
+    const int u = wr * MB * 2 * LC1 + li;
+#pragma unroll
+    for (int j = 0; j < NCH; ++j) xb[j] = u * (PS1 * 4) + 16 * (lg ^ ((u + j) & (NCH - 1)));
+  }
   auto load_b = [&](int s, f32x4* dst) {
     const int tap = s / KC1, kc = s % KC1, ky = tap / 3, kx = tap % 3;
 #pragma unroll
     for (int mb = 0; mb < MB; ++mb) {
-      const int r = wr * MB + mb;
-      const int lp = (2 * r + ky) * LC1 + (kx & 1) * 17 + li + (kx >> 1);
-      dst[mb] = *reinterpret_cast<const f32x4*>(&t1[t1c(lp, kc * 4 + lg)]);
+      if constexpr (KEYED) {
+        const int uc = (2 * mb + ky) * LC1 + (kx & 1) * 17 + (kx >> 1);
+        dst[mb] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(t1) + (xb[uc % NCH] ^ (64 * kc)) +
+                                                  uc * (PS1 * 4));
+      } else {
+        const int r = wr * MB + mb;
+        const int lp = (2 * r + ky) * LC1 + (kx & 1) * 17 + li + (kx >> 1);
+        dst[mb] = *reinterpret_cast<const f32x4*>(&t1[t1c(lp, kc * 4 + lg)]);
+      }
     }
   };
   f32x4 bq[2][MB];

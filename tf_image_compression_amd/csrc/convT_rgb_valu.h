@@ -34,9 +34,10 @@ namespace tic {
 // the position in an LDS tile of pitch PS floats per position and LC positions per row, so
 // that offset (-1, 0) is self - LC*PS and (0, -1) is self - PS.  `w` is [3][3][3][CIN].
 // rgb_out_fma_g: the same with chunk c4 of offset (dy, dx) loaded by ld(dy, dx, c4); PK
-// selects packed fmas (v_pk_fma_f32, whose two weights must sit in an aligned SGPR pair —
-// s_mov repacking per instruction) or two interleaved plain v_fma_f32 chains (one SGPR
-// operand each).  Weights in global memory (WG) are read through the constant address
+// selects packed fmas (v_pk_fma_f32, whose two weights must sit in an aligned SGPR pair: read
+// from the host's pair-interleaved copy behind the raw kernel, pair_slot below; weights staged
+// in LDS keep the raw layout) or two interleaved plain v_fma_f32 chains (one SGPR operand
+// each).  Weights in global memory (WG) are read through the constant address
 // space: wave-uniform scalar loads even where the kernel also stores to global memory
 // earlier on the path (the persistent forms), which would otherwise make them vector
 // loads; weights staged in LDS (!WG) are read as they are.  Offsets and phases are
@@ -53,6 +54,12 @@ constexpr int tap(int p, int d) { return p ? 1 : (d == 0 ? 0 : 2); }
 // 2 -> 0,1; 3 -> 0
 constexpr int nphase(int off) { return off == 0 ? 4 : off == 3 ? 1 : 2; }
 constexpr int phase(int off, int k) { return off == 1 ? 2 * k : k; }
+
+// Behind the raw kernel the host (tic_finalize) keeps the paired phases' weights interleaved,
+// [4 slots][3 co][CIN][2]: slot 0 / 1 offset (0,0) phases (0,1) / (2,3), slot 2 offset (0,-1)
+// phases (0,2), slot 3 offset (-1,0) phases (0,1).  The scalar loads then deliver a packed
+// fma's two weights as the aligned SGPR pair it needs, without an s_mov per weight.
+constexpr int pair_slot(int off, int pa) { return off == 0 ? (pa >> 1) : off + 1; }
 
 template <int CIN, int OFF, int PA, class W>
 __device__ __forceinline__ W wrow(W w, int co) {
@@ -71,11 +78,13 @@ __device__ __forceinline__ void chains(const float (&x)[CIN], W w, f32x4 (&acc)[
     } else {
       const W wb = wrow<CIN, OFF, PB>(w, co);
       if constexpr (PK) {
+        constexpr bool WG = std::is_same<W, cfp>::value;  // global weights: the interleaved copy
+        const W wp = w + 27 * CIN + (pair_slot(OFF, PA) * 3 + co) * CIN * 2;
         f32x2 s2 = {acc[PA][co], acc[PB][co]};
 #pragma unroll
         for (int ci = 0; ci < CIN; ++ci) {
           const f32x2 xx = {x[ci], x[ci]};
-          const f32x2 ww = {wa[ci], wb[ci]};
+          const f32x2 ww = WG ? f32x2{wp[2 * ci], wp[2 * ci + 1]} : f32x2{wa[ci], wb[ci]};
           s2 = __builtin_elementwise_fma(xx, ww, s2);
         }
         acc[PA][co] = s2.x;
@@ -146,8 +155,24 @@ __device__ __forceinline__ void rgb_out_epilogue(const RgbOutArgs& a, const f32x
   }
 }
 
+// Four clipped values in [0, 255] to four bytes, round half to even (np.around): one
+// v_cvt_pk_u8_f32 per byte.  The instruction rounds to nearest even on its own (measured over
+// every float of [0, 255] by tools/probes/cvt_pk_u8.hip; tests/test_gpu_head_tail_trim.py pins
+// the ties through the whole decoder at P = 128, where every tile of the fused and the unfused
+// form is full-width and takes the chunk path below — at P = 16 the same test pins the
+// element-wise rintf path), so no v_rndne_f32 goes before it.
+__device__ __forceinline__ uint32_t rgb_out_pack4(const f32x4 v) {
+  uint32_t w = __builtin_amdgcn_cvt_pk_u8_f32(v.x, 0, 0);
+  w = __builtin_amdgcn_cvt_pk_u8_f32(v.y, 1, w);
+  w = __builtin_amdgcn_cvt_pk_u8_f32(v.z, 2, w);
+  return __builtin_amdgcn_cvt_pk_u8_f32(v.w, 3, w);
+}
+
 // Write the staged output tile (2TH x 2TW pixels at input origin (gy0, gx0) of image nimg):
-// whole 16-byte row chunks when the tile is interior and aligned, else element-wise.
+// whole 16-byte row chunks when the tile's rows are complete and aligned, else element-wise.
+// The chunk path has at most one u8 chunk (exactly three f32 chunks) per thread: its row and
+// column come from the thread index by constant divisors, and its address is the tile's
+// (scalar) plus a 32-bit lane offset.
 template <int TH, int TW, int NT>
 __device__ __forceinline__ void rgb_out_store(const RgbOutArgs& a, const float* lout, int tid, int gy0, int gx0,
                                               int nimg) {
@@ -161,16 +186,13 @@ __device__ __forceinline__ void rgb_out_store(const RgbOutArgs& a, const float* 
     const bool vec = full && ((Wo * 3) % 16 == 0) && ((ox0 * 3) % 16 == 0) && ((uintptr_t)a.out_u8 % 16 == 0);
     if (vec) {
       constexpr int CH = OW / 16;  // 16-byte chunks per tile row (OW u8 bytes)
-      for (int e = tid; e < rows * CH; e += NT) {
-        const int rr = e / CH, ch = e % CH;
-        const float* s = &lout[rr * OW + ch * 16];
-        uint32_t wv[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-          wv[k] = (uint32_t)rintf(s[4 * k]) | ((uint32_t)rintf(s[4 * k + 1]) << 8) |
-                  ((uint32_t)rintf(s[4 * k + 2]) << 16) | ((uint32_t)rintf(s[4 * k + 3]) << 24);
-        *reinterpret_cast<uint4*>(a.out_u8 + (row_base + (size_t)rr * Wo) * 3 + ch * 16) =
-            make_uint4(wv[0], wv[1], wv[2], wv[3]);
+      static_assert(OW % 16 == 0 && 2 * TH * CH <= NT, "one u8 chunk per thread");
+      const int rr = tid / CH, ch = tid % CH;
+      if (rr < rows) {
+        const f32x4* s = reinterpret_cast<const f32x4*>(&lout[rr * OW + ch * 16]);
+        uint8_t* const tile = a.out_u8 + row_base * 3;
+        *reinterpret_cast<uint4*>(tile + (unsigned)(rr * Wo * 3 + ch * 16)) =
+            make_uint4(rgb_out_pack4(s[0]), rgb_out_pack4(s[1]), rgb_out_pack4(s[2]), rgb_out_pack4(s[3]));
       }
     } else {
       for (int e = tid; e < rows * cols * 3; e += NT) {
@@ -183,10 +205,14 @@ __device__ __forceinline__ void rgb_out_store(const RgbOutArgs& a, const float* 
     const bool vec = full && ((Wo * 3) % 4 == 0) && ((ox0 * 3) % 4 == 0) && ((uintptr_t)a.out_f32 % 16 == 0);
     if (vec) {
       constexpr int CH = OW / 4;  // 16-byte chunks per tile row (OW floats)
-      for (int e = tid; e < rows * CH; e += NT) {
-        const int rr = e / CH, ch = e % CH;
-        *reinterpret_cast<f32x4*>(a.out_f32 + (row_base + (size_t)rr * Wo) * 3 + ch * 4) =
-            *reinterpret_cast<const f32x4*>(&lout[rr * OW + ch * 4]);
+      static_assert((2 * TH * CH) % NT == 0, "whole f32 chunks per thread");
+      float* const tile = a.out_f32 + row_base * 3;
+#pragma unroll
+      for (int i = 0; i < 2 * TH * CH / NT; ++i) {
+        const int e = i * NT + tid, rr = e / CH, ch = e % CH;
+        if (rr < rows)
+          *reinterpret_cast<f32x4*>(tile + (unsigned)(rr * Wo * 3 + ch * 4)) =
+              *reinterpret_cast<const f32x4*>(&lout[rr * OW + ch * 4]);
       }
     } else {
       for (int e = tid; e < rows * cols * 3; e += NT) {

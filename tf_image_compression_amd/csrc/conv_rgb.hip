@@ -50,7 +50,12 @@ int enc01_variants() { return 5; }
 template <int C0, int C1, int TH1, bool CMP>
 static bool enc01_th(bool u8_input, const Enc01Args& a, int n, hipStream_t s) {
   dim3 grid((a.W2 + 15) / 16, (a.H2 + TH1 - 1) / TH1, n);
-  if (u8_input)
+  if (a.tstamp) {  // TIC_ENC01_TIMING: the instance with the phase timestamps compiled in
+    if (u8_input)
+      hipLaunchKernelGGL((enc01_kernel<C0, C1, TH1, true, CMP, true>), grid, dim3(256), 0, s, a);
+    else
+      hipLaunchKernelGGL((enc01_kernel<C0, C1, TH1, false, CMP, true>), grid, dim3(256), 0, s, a);
+  } else if (u8_input)
     hipLaunchKernelGGL((enc01_kernel<C0, C1, TH1, true, CMP>), grid, dim3(256), 0, s, a);
   else
     hipLaunchKernelGGL((enc01_kernel<C0, C1, TH1, false, CMP>), grid, dim3(256), 0, s, a);

@@ -63,7 +63,7 @@ struct Dec10 {
 
   // float offset of channel chunk c4 of decode_0 input position pos in yt
   __device__ __forceinline__ static int ychunk(int pos, int c4) {
-    if constexpr (CMP) return pos * PSY + 4 * (c4 ^ ((pos / GRP) % NCH));
+    if constexpr (CMP) return pos * PSY + 4 * (c4 ^ (int)(((unsigned)pos / GRP) % NCH));  // pos >= 0 wherever the result is used
     else return pos * PSY + 4 * c4;
   }
 
@@ -75,8 +75,31 @@ struct Dec10 {
                        ((tap * KC + kc) * 4 * C0 * 4 + nb * 64) * 4);
   }
 
-  // decode_1's input rows m0-1 .. m0+3, columns q0-1 .. q0+15 (zero outside) into registers
+  // decode_1's input rows m0-1 .. m0+3, columns q0-1 .. q0+15 (zero outside) into registers,
+  // through a buffer resource over image nimg as conv3x3_kernel stages its tile: a 32-bit lane
+  // offset, a position outside the image (or past the tile's last chunk) given an offset past
+  // the resource's end, which reads zero — no 64-bit address, zero fill or branch per chunk.
+  // The chunk index is the same for every i (NT % C4 == 0) and the position advances by a
+  // constant.  Images of 4 GB or more keep the pointer form.
   __device__ __forceinline__ static void issue(const Dec10Args& a, f32x4 (&pre)[NIT], int q0, int m0, int nimg, int tid) {
+    static_assert(NT % C4 == 0, "chunk index per thread");
+    const size_t img_bytes = (size_t)a.H * a.W * C1 * 4;
+    if (img_bytes < 0xFFFFFF00ull) {
+      const __amdgpu_buffer_rsrc_t irs = weight_rsrc(a.in + (size_t)nimg * a.H * a.W * C1, (int)(unsigned)img_bytes);
+      const int c4 = tid % C4, p0 = tid / C4;
+#pragma unroll
+      for (int i = 0; i < NIT; ++i) {
+        const int pe = p0 + i * (NT / C4);
+        const int row = pe / LCX, col = pe - row * LCX;
+        const int iy = m0 - 1 + row, ix = q0 - 1 + col;
+        const bool inside = (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W &&
+                            ((i + 1) * NT <= NSTAGE || pe < LRX * LCX);
+        const unsigned off = inside ? ((unsigned)(iy * a.W + ix) * C1 + c4 * 4) * 4u : 0xFFFFFFF0u;
+        if constexpr (PROBE & 4) pre[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+        else pre[i] = weight_frag(irs, (int)off, 0);
+      }
+      return;
+    }
 #pragma unroll
     for (int i = 0; i < NIT; ++i) {
       const int e = i * NT + tid;
@@ -141,22 +164,38 @@ struct Dec10 {
         for (int nb = 0; nb < NB; ++nb) av[p][nb] = wglob(a, p, nb, li, lg);
     }
   }
+  // Byte offset in yt of channel chunk lg of position upos + 2 li (upos wave-uniform, so its
+  // share of the offset and of the swizzle key is scalar work); chunk 4 nb + lg of the same
+  // position lies at ynb(offset, nb): the key's high bits flip 4 nb, its low bits only lg.
+  __device__ __forceinline__ static int ybyte(int pos, int lg) { return 4 * ychunk(pos, lg); }
+  __device__ __forceinline__ static int ylane(int upos, int li, int lg) {
+    constexpr int PB = 4 * PSY;
+    if constexpr (!CMP) return upos * PB + li * (2 * PB) + 16 * lg;
+    else if constexpr (GRP == 1) return upos * PB + li * (2 * PB) + 16 * (lg ^ ((upos + 2 * li) & (NCH - 1)));
+    else if constexpr (GRP == 2) return upos * PB + li * (2 * PB) + 16 * (lg ^ (((upos >> 1) + li) & (NCH - 1)));
+    else return ybyte(upos + 2 * li, lg);
+  }
+  __device__ __forceinline__ static int ynb(int off, int nb) { return CMP ? off ^ (64 * nb) : off + 64 * nb; }
+  __device__ __forceinline__ static f32x4* yat(float* yt, int byte) {
+    return reinterpret_cast<f32x4*>(reinterpret_cast<char*>(yt) + byte);
+  }
+  static_assert(!CMP || (PSY % (4 * NCH) == 0 && (NCH & (NCH - 1)) == 0 && NCH >= 4), "ynb");
+
   // + bias, ReLU -> yt
-  __device__ __forceinline__ static void put_interior(const Dec10Args& a, float* yt, const f32x4 (&acc)[4][NB], int wave, int li,
-                                      int lg) {
+  __device__ __forceinline__ static void put_interior(float* yt, const f32x4 (&acc)[4][NB], const f32x4 (&bb)[NB], int wave,
+                                                      int li, int lg) {
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
       const int py = p >> 1, px = p & 1;
+      const int off = ylane((1 + 2 * wave + py) * LCY + 1 + px, li, lg);
 #pragma unroll
       for (int nb = 0; nb < NB; ++nb) {
-        const int co = nb * 16 + lg * 4;
-        const f32x4 bb = *reinterpret_cast<const f32x4*>(a.b1 + co);
         f32x4 v = acc[p][nb];
-        v.x = fmaxf(__fadd_rn(v.x, bb.x), 0.f);
-        v.y = fmaxf(__fadd_rn(v.y, bb.y), 0.f);
-        v.z = fmaxf(__fadd_rn(v.z, bb.z), 0.f);
-        v.w = fmaxf(__fadd_rn(v.w, bb.w), 0.f);
-        *reinterpret_cast<f32x4*>(&yt[ychunk((1 + 2 * wave + py) * LCY + 1 + 2 * li + px, co / 4)]) = v;
+        v.x = fmaxf(__fadd_rn(v.x, bb[nb].x), 0.f);
+        v.y = fmaxf(__fadd_rn(v.y, bb[nb].y), 0.f);
+        v.z = fmaxf(__fadd_rn(v.z, bb[nb].z), 0.f);
+        v.w = fmaxf(__fadd_rn(v.w, bb[nb].w), 0.f);
+        *yat(yt, ynb(off, nb)) = v;
       }
     }
   }
@@ -199,43 +238,61 @@ struct Dec10 {
     }
   }
   // + bias, ReLU (zero where the position lies above / left of the image: decode_0's zero
-  // padding) -> yt
-  __device__ __forceinline__ static void put_halo(const Dec10Args& a, float* yt, const f32x4 (&hacc)[2][HNB], bool row,
+  // padding) -> yt.  The row above lies outside exactly when m0 == 0 and the column left when
+  // q0 == 0 — both uniform over the tile — and with m0 == 0 the column's first position
+  // (row -1) besides; a tile away from both borders takes no select.
+  __device__ __forceinline__ static void put_halo(float* yt, const f32x4 (&hacc)[2][HNB], const f32x4 (&hb)[HNB], bool row,
                                                   int nb0, int li, int lg, int q0, int m0) {
+    const bool tile_in = m0 >= 1 && q0 >= 1;
 #pragma unroll
-    for (int q = 0; q < 2; ++q)
+    for (int q = 0; q < 2; ++q) {
+      int off;
+      bool use, inside;
+      if (row) {
+        off = ylane(1 + q, li, lg);  // row 0, column 1 + 2 li + q
+        use = true, inside = m0 >= 1;
+      } else {
+        const int ry = 2 * li - 1 + q;  // column 0
+        off = ybyte(ry * LCY, lg);  // ry = -1 only in a lane `use` leaves out
+        use = q ? li <= TA : (li >= 1 && li <= TA);
+        inside = q0 >= 1 && (m0 >= 1 || ry >= 1);
+      }
+      if (!use) continue;
 #pragma unroll
       for (int nb = 0; nb < HNB; ++nb) {
-        const int co = (nb0 + nb) * 16 + lg * 4;
-        int ry, cy;
-        bool use;
-        if (row) {
-          ry = 0, cy = 1 + 2 * li + q, use = true;
-        } else {
-          ry = q ? 2 * li : 2 * li - 1, cy = 0, use = q ? li <= TA : (li >= 1 && li <= TA);
-        }
-        if (!use) continue;
-        const bool inside = 2 * m0 - 1 + ry >= 0 && 2 * q0 - 1 + cy >= 0;
-        const f32x4 bb = *reinterpret_cast<const f32x4*>(a.b1 + co);
+        const f32x4 bb = hb[nb];
         f32x4 v = hacc[q][nb];
-        v.x = inside ? fmaxf(__fadd_rn(v.x, bb.x), 0.f) : 0.f;
-        v.y = inside ? fmaxf(__fadd_rn(v.y, bb.y), 0.f) : 0.f;
-        v.z = inside ? fmaxf(__fadd_rn(v.z, bb.z), 0.f) : 0.f;
-        v.w = inside ? fmaxf(__fadd_rn(v.w, bb.w), 0.f) : 0.f;
-        *reinterpret_cast<f32x4*>(&yt[ychunk(ry * LCY + cy, co / 4)]) = v;
+        v.x = fmaxf(__fadd_rn(v.x, bb.x), 0.f);
+        v.y = fmaxf(__fadd_rn(v.y, bb.y), 0.f);
+        v.z = fmaxf(__fadd_rn(v.z, bb.z), 0.f);
+        v.w = fmaxf(__fadd_rn(v.w, bb.w), 0.f);
+        // `inside` alone decides; the tile-uniform term in front only lets the select be branched over
+        if (!tile_in && !inside) v = f32x4{0.f, 0.f, 0.f, 0.f};
+        *yat(yt, ynb(off, nb0 + nb)) = v;
       }
+    }
   }
 
   // ---- 4. decode_0 of input position (r, c) of the tile on the VALU (acc3 zeroed) ----
   __device__ __forceinline__ static void decode0(const Dec10Args& a, const float* yt, const float* wsh, f32x4 (&acc3)[4], int r,
                                  int c) {
     if constexpr ((PROBE & 2) != 0) acc3[0][0] = yt[((r + 1) * LCY + (c + 1)) * PSY];
-    else
+    else {
+      // byte offset of chunk 0 of the four input offsets' positions; chunk c4 of a position
+      // lies at the position's chunk 0 ^ 16 c4 (CMP: the key only permutes the chunks) or
+      // + 16 c4 — in bytes, so that each read's address is one xor (or the read's immediate)
+      int y0[2][2];
+#pragma unroll
+      for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+        for (int dx = 0; dx < 2; ++dx) y0[dy][dx] = 4 * ychunk((r + 1 - dy) * LCY + c + 1 - dx, 0);
       rgb_out_fma_g<C0, PK, !WSH>(
           [&](int dy, int dx, int c4) {
-            return *reinterpret_cast<const f32x4*>(&yt[ychunk((r + 1 + dy) * LCY + c + 1 + dx, c4)]);
+            const int o = y0[-dy][-dx];
+            return *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(yt) + (CMP ? o ^ (16 * c4) : o + 16 * c4));
           },
           WSH ? wsh : a.rgb.wraw, acc3);
+    }
   }
 
   // One tile, its input already in xt (and a barrier behind it): decode_1 by MFMA into yt,
@@ -247,16 +304,24 @@ struct Dec10 {
     const int lane = tid & 63, li = lane & 15, lg = lane >> 4;
     f32x4 acc[4][NB];
     interior(a, xt, av, acc, wave, li, lg, false);
-    if constexpr (!CMP) put_interior(a, yt, acc, wave, li, lg);
+    // decode_1's biases, loaded once and behind the K loop (their latency passes under the halo)
+    f32x4 bb[NB], hb[HNB];
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb) bb[nb] = *reinterpret_cast<const f32x4*>(a.b1 + nb * 16 + lg * 4);
+    if constexpr (!CMP) put_interior(yt, acc, bb, wave, li, lg);
     const bool row = (wave & 1) == 0;
     const int nb0 = (wave >> 1) * HNB;
     f32x4 hacc[2][HNB];
+    if (!(PROBE & 32) && wave < HW) {
+#pragma unroll
+      for (int nb = 0; nb < HNB; ++nb) hb[nb] = *reinterpret_cast<const f32x4*>(a.b1 + (nb0 + nb) * 16 + lg * 4);
+    }
     if (!(PROBE & 32) && wave < HW) halo(a, xt, hacc, row, nb0, li, lg);
     if constexpr (CMP) {  // xt lives inside yt: every read of it precedes the first write
       __syncthreads();
-      put_interior(a, yt, acc, wave, li, lg);
+      put_interior(yt, acc, bb, wave, li, lg);
     }
-    if (!(PROBE & 32) && wave < HW) put_halo(a, yt, hacc, row, nb0, li, lg, q0, m0);
+    if (!(PROBE & 32) && wave < HW) put_halo(yt, hacc, hb, row, nb0, li, lg, q0, m0);
     __syncthreads();
 
     // decode_0; output tile staged in the dead decode_1 input tile (or, when it is too small,

@@ -67,7 +67,8 @@ struct RgbOutArgs {
   const float* in;     // [N,H,W,Cin]
   const float* wp;     // dense sub-pixel form: [4 off][Cin/16][16 rows][4][4]
   const float* wp2;    // scatter form: [2 rb][Cin/16][4 g][16 rows][4 t]
-  const float* wraw;   // VALU form: the TF kernel as-is, [3][3][3][Cin]
+  const float* wraw;   // VALU form: the TF kernel as-is, [3][3][3][Cin], then the paired phases' weights
+                       // interleaved, [4][3][Cin][2] (convT_rgb_valu.h pair_slot)
   const float* bias;   // [3]
   uint8_t* out_u8;     // [N,2H,2W,3] or nullptr
   float* out_f32;      // [N,2H,2W,3] or nullptr

@@ -1741,8 +1741,22 @@ int tic_finalize(tic_handle* h) {
       pack_rgb_out_scatter(l.k.data(), l.def.cin, &w2);
       HIP_TRY(hipMalloc((void**)&l.d_w2, w2.size() * sizeof(float)));
       HIP_TRY(hipMemcpy(l.d_w2, w2.data(), w2.size() * sizeof(float), hipMemcpyHostToDevice));
-      HIP_TRY(hipMalloc((void**)&l.d_w3, l.k.size() * sizeof(float)));
-      HIP_TRY(hipMemcpy(l.d_w3, l.k.data(), l.k.size() * sizeof(float), hipMemcpyHostToDevice));
+      // the TF kernel as-is, then the weights of the phase pairs the VALU form advances with one
+      // packed fma interleaved (convT_rgb_valu.h pair_slot): [4 slots][3 co][Cin][2]
+      std::vector<float> w3(l.k);
+      const int cin = l.def.cin;
+      auto tap = [](int p, int d) { return p ? 1 : (d == 0 ? 0 : 2); };
+      static const int pairs[4][3] = {{0, 0, 1}, {0, 2, 3}, {1, 0, 2}, {2, 0, 1}};  // offset, phase a, phase b
+      for (const auto& pr : pairs)
+        for (int co = 0; co < 3; ++co)
+          for (int ci = 0; ci < cin; ++ci)
+            for (int k = 0; k < 2; ++k) {
+              const int ph = pr[1 + k];
+              const int ky = tap(ph >> 1, -(pr[0] >> 1)), kx = tap(ph & 1, -(pr[0] & 1));
+              w3.push_back(l.k[(size_t)((ky * 3 + kx) * 3 + co) * cin + ci]);
+            }
+      HIP_TRY(hipMalloc((void**)&l.d_w3, w3.size() * sizeof(float)));
+      HIP_TRY(hipMemcpy(l.d_w3, w3.data(), w3.size() * sizeof(float), hipMemcpyHostToDevice));
     }
     HIP_TRY(hipMalloc((void**)&l.d_w, wp.size() * sizeof(float)));
     HIP_TRY(hipMemcpy(l.d_w, wp.data(), wp.size() * sizeof(float), hipMemcpyHostToDevice));
@@ -2566,8 +2580,8 @@ int tic_layer_kernel(const tic_handle* h, int i, int n, char* name, int cap) {
       int v = iv != l.tuned_var.end() ? iv->second : tic::kEnc01Default;
       if (const char* t = getenv("TIC_ENC01_VARIANT")) v = atoi(t);
       static const int th1[5] = {2, 4, 2, 4, 8};
-      snprintf(buf, sizeof buf, "enc01_kernel<%d,%d,%d,%s,%s>", d.cout, h->layers[1].def.cout, th1[v % 5],
-               tf[!h->rmbe()], tf[v >= 2]);
+      snprintf(buf, sizeof buf, "enc01_kernel<%d,%d,%d,%s,%s,%s>", d.cout, h->layers[1].def.cout, th1[v % 5],
+               tf[!h->rmbe()], tf[v >= 2], tf[getenv("TIC_ENC01_TIMING") != nullptr]);
     }
   } else if (i == 0 || i == L - 1) {
     auto iv = l.tuned_var.find(n);
