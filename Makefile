@@ -7,7 +7,7 @@ BUILD    := build
 LIB      := tf_image_compression_amd/libtic.so
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -Iinclude -I$(CSRC)
 KERNELS  := conv_s1 conv_s2 conv_t2 conv_rgb conv_chain image_ops
-OBJS     := $(addprefix $(BUILD)/,$(addsuffix .o,$(KERNELS))) $(BUILD)/tic_msssim.o $(BUILD)/range_coder.o \
+OBJS     := $(addprefix $(BUILD)/,$(addsuffix .o,$(KERNELS))) $(BUILD)/tic_entropy.o $(BUILD)/range_coder.o \
             $(BUILD)/host_util.o
 HDRS     := $(wildcard $(CSRC)/*.h) include/tic.h
 
@@ -16,10 +16,12 @@ all: $(LIB)
 $(BUILD)/%.o: $(CSRC)/%.hip $(HDRS) | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-# tic_msssim.cpp includes tic_image_batch.cpp, which includes tic_runtime.cpp: the host runtime,
-# the image-list entries and the MS-SSIM entries are one translation unit (the entries use the
-# handle's internals; tic_runtime.cpp itself stays as the shipped tuning states were stamped)
-$(BUILD)/tic_msssim.o: $(CSRC)/tic_msssim.cpp $(CSRC)/tic_image_batch.cpp $(CSRC)/tic_runtime.cpp $(HDRS) | $(BUILD)
+# tic_entropy.cpp includes tic_msssim.cpp, which includes tic_image_batch.cpp, which includes
+# tic_runtime.cpp: the host runtime, the image-list entries, the MS-SSIM entries and the entropy
+# coder are one translation unit (the entries use the handle's internals; tic_runtime.cpp itself
+# stays as the shipped tuning states were stamped)
+$(BUILD)/tic_entropy.o: $(CSRC)/tic_entropy.cpp $(CSRC)/tic_msssim.cpp $(CSRC)/tic_image_batch.cpp \
+                        $(CSRC)/tic_runtime.cpp $(HDRS) | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
 
 $(BUILD)/range_coder.o: $(CSRC)/range_coder.cpp include/tic.h | $(BUILD)
@@ -44,7 +46,16 @@ $(ASAN_BIN): tests/native/host_fuzz.cpp $(CSRC)/range_coder.cpp $(CSRC)/host_uti
 	g++ -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=all \
 	    -Iinclude -o $@ tests/native/host_fuzz.cpp $(CSRC)/range_coder.cpp $(CSRC)/host_util.cpp
 
+# The segmented-stream host code (tic_rcseg_*) under the same sanitizers, with its own harness.
+RCSEG_BIN := $(BUILD)/rcseg_fuzz_asan
+asan-rcseg: $(RCSEG_BIN)
+	$(RCSEG_BIN) $(BUILD)
+
+$(RCSEG_BIN): tests/native/rcseg_fuzz.cpp $(CSRC)/range_coder.cpp include/tic.h | $(BUILD)
+	g++ -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=all \
+	    -Iinclude -o $@ tests/native/rcseg_fuzz.cpp $(CSRC)/range_coder.cpp
+
 clean:
 	rm -rf $(BUILD) $(LIB)
 
-.PHONY: all clean asan
+.PHONY: all clean asan asan-rcseg

@@ -7,6 +7,8 @@ submit/2 block-effect post-filter (``--rmbe``, submit/2/decoder.py:184).
 Reference: /root/reference/decode.py:20-76 (flags), :79-140 (range decoding, file-name
 parsing), :143-264 (uncompress).  ``-g`` accepts -1..7 (-1 is accepted for
 compatibility; there is no CPU path, so it maps to device 0 with a warning).
+``--entropy device`` reads the segmented-stream containers ``encode.py --entropy device``
+writes and decodes them on the GPU, a group of files per call.
 """
 import argparse
 import os
@@ -40,7 +42,13 @@ def my_parse_args(argv=None):
     p.add_argument("--batch-images", type=int, default=1, metavar="N",
                    help="decode up to N files (at most 512 patches) as one patch batch; same files and "
                         "output as 1, the default (one image per launch sequence)")
-    return p.parse_args(argv)
+    p.add_argument("--entropy", choices=["host", "device"], default="host",
+                   help="host: single-stream files (the default); device: segmented-stream containers "
+                        "(encode.py --entropy device), range-decoded on the GPU")
+    args = p.parse_args(argv)
+    if args.entropy == "device" and args.raw:
+        p.error("--raw files hold no entropy-coded stream: it cannot be combined with --entropy device")
+    return args
 
 
 def get_img_info(filename, config):
@@ -117,6 +125,11 @@ def uncompress(model, args):
             raw = np.fromfile(path, np.uint8)
             seq = np.unpackbits(raw)[:seq_len] if Q == 2 else raw[:seq_len]
         else:
+            from tf_image_compression_amd import entropy
+            with open(path, "rb") as f:
+                if entropy.is_container(f.read(4)):
+                    raise ValueError(f"{path} is a segmented stream (encode.py --entropy device): "
+                                     "decode it with --entropy device")
             seq = apply_range_decoder(seq_len, path, cum_freq)
         return seq.astype(np.uint8).reshape(-1, eh, ew, ec), height, width   # decode.py:204-208
 
@@ -128,7 +141,17 @@ def uncompress(model, args):
     filenames = [f for f in sorted(os.listdir(input_dir)) if f.endswith(".encoded")]
     if args.batch_images < 1:
         raise ValueError("--batch-images must be at least 1")
-    if args.batch_images == 1:
+    if args.entropy == "device":
+        # groups as for --batch-images; every container is validated on the host (tic_rcseg_parse),
+        # then the group's containers are decoded on the GPU in one call
+        sizes = [get_img_info(f, config)[1:] for f in filenames]
+        for group in ic.plan_batches(sizes, P, args.batch_images):
+            streams = [(Path(input_dir) / filenames[i]).read_bytes() for i in group]
+            images = ic.decode_streams_to_images(streams, [sizes[i] for i in group], cum_freq,
+                                                 post_filter=post is not None)
+            for i, recons in zip(group, images):
+                store(filenames[i], recons)
+    elif args.batch_images == 1:
         for filename in filenames:
             symbols, height, width = read_symbols(filename)
             # decode -> concat_patches -> (rmbe) -> np.around, all on the GPU

@@ -12,7 +12,10 @@ CUDA_VISIBLE_DEVICES; ``-p`` names the TF checkpoint prefix (read by tf_checkpoi
 ``sess.run`` batches of 64.  Extra optional flags: ``--norm`` (channel statistics
 npz), ``--dist`` (symbol distribution npy), ``--synthetic-weights`` (seeded weights when
 no checkpoint exists), ``--raw`` (store bit-packed symbols, no entropy coding),
-``--batch-images N`` (N > 1: consecutive images share one patch batch, image_codec.py).
+``--batch-images N`` (N > 1: consecutive images share one patch batch, image_codec.py),
+``--entropy device`` (the symbols stay on the GPU and are range-coded there, one segment of
+``--segment L`` symbols per lane; each file then holds one segmented-stream container,
+tf_image_compression_amd/entropy.py, which ``decode.py --entropy device`` reads).
 """
 import argparse
 import os
@@ -48,7 +51,15 @@ def my_parse_args(argv=None):
     p.add_argument("--batch-images", type=int, default=1, metavar="N",
                    help="encode up to N images (at most 512 patches) as one patch batch; same files and "
                         "output as 1, the default (one image per launch sequence)")
-    return p.parse_args(argv)
+    p.add_argument("--entropy", choices=["host", "device"], default="host",
+                   help="host: the single-stream range coder (the default, the reference's format); device: "
+                        "range-code on the GPU into one segmented-stream container per file")
+    p.add_argument("--segment", type=int, default=2048, metavar="L",
+                   help="symbols per segment of --entropy device (multiple of 4, 4..16384)")
+    args = p.parse_args(argv)
+    if args.entropy == "device" and args.raw:
+        p.error("--raw stores symbols without entropy coding: it cannot be combined with --entropy device")
+    return args
 
 
 def symbol_table(args, config):
@@ -115,7 +126,20 @@ def compress(model, args):
     image_paths = utils.read_image_list(args.data_list)
     if args.batch_images < 1:
         raise ValueError("--batch-images must be at least 1")
-    if args.batch_images == 1:
+    if args.entropy == "device":
+        # groups as for --batch-images; the symbols of a group are coded on the GPU in one call
+        sizes = [utils.image_size(p) for p in image_paths]
+        shape = tuple(codec.code_shape)
+        for group in ic.plan_batches(sizes, P, args.batch_images):
+            images = [utils.imread(image_paths[i]) for i in group]
+            streams = ic.encode_images_to_streams(images, cum_freq, segment=args.segment)
+            for i, image, stream in zip(group, images, streams):
+                seq_len = ic.num_patches(*image.shape[:2]) * int(np.prod(shape))
+                encodepath = get_encodepath(image_paths[i], image, seq_len, args, config, shape)
+                with open(encodepath, "wb") as f:
+                    f.write(stream)
+                print(f"encodepath: {encodepath}")
+    elif args.batch_images == 1:
         for image_path in image_paths:
             image = utils.imread(image_path)
             store(image_path, image, ic.encode_image(image))     # [n, eh, ew, ec] uint8

@@ -11,7 +11,10 @@ Flags as encode.py (``-m -g -p -v``, ``--norm``, ``--dist``, ``--synthetic-weigh
 One line per image (PSNR, MS-SSIM, MS-SSIM in dB = -10 log10(1 - ms), estimated bpp), then the
 dataset line: evaluate()'s PSNR formula over all images (sum of SSE over sum of dims), the mean
 MS-SSIM (images with a side below 161 have none and are left out) and total estimated bits over
-total pixels.  Without a distribution file the rate columns are omitted.
+total pixels.  Without a distribution file the rate columns are omitted.  ``--entropy device``
+(with ``--segment L``) also range-codes every image's symbols on the GPU into a segmented
+stream (tf_image_compression_amd/entropy.py) and prints its real size, ``coded_bytes``, and the
+bpp from it.
 """
 import argparse
 import json
@@ -45,6 +48,11 @@ def my_parse_args(argv=None):
     p.add_argument("--batch-images", type=int, default=1, metavar="N",
                    help="evaluate up to N images (at most 512 patches) as one patch batch; same values as 1")
     p.add_argument("--json", type=str, default="", metavar="OUT", help="also write the results as JSON")
+    p.add_argument("--entropy", choices=["host", "device"], default="host",
+                   help="device: also range-code every image's symbols on the GPU (segmented streams) and "
+                        "print the real coded_bytes and the bpp from them beside the estimate")
+    p.add_argument("--segment", type=int, default=2048, metavar="L",
+                   help="symbols per segment of --entropy device (multiple of 4, 4..16384)")
     args = p.parse_args(argv)
     if args.batch_images < 1:
         p.error("--batch-images must be at least 1")
@@ -75,13 +83,19 @@ def dataset_summary(rows) -> dict:
         psnr = float(mse2psnr(np.float64(sse) / dims)) if dims else float("nan")
     mean_ms = float(np.mean(ms)) if ms else float("nan")
     bits = None if any(r["est_bits"] is None for r in rows) else float(sum(r["est_bits"] for r in rows))
-    return {"n_images": len(rows), "n_msssim": len(ms), "pixels": pixels, "sse": sse, "psnr": psnr,
-            "msssim": mean_ms, "msssim_db": msssim_db(mean_ms), "est_bits": bits,
-            "est_bpp": None if bits is None or not pixels else bits / pixels}
+    out = {"n_images": len(rows), "n_msssim": len(ms), "pixels": pixels, "sse": sse, "psnr": psnr,
+           "msssim": mean_ms, "msssim_db": msssim_db(mean_ms), "est_bits": bits,
+           "est_bpp": None if bits is None or not pixels else bits / pixels}
+    if rows and all("coded_bytes" in r for r in rows):  # --entropy device
+        out["coded_bytes"] = sum(r["coded_bytes"] for r in rows)
+        out["coded_bpp"] = 8.0 * out["coded_bytes"] / pixels if pixels else None
+    return out
 
 
 def _line(name, r) -> str:
     rate = "" if r["est_bpp"] is None else f"  est_bpp {r['est_bpp']:.4f}"
+    if r.get("coded_bytes") is not None:
+        rate += f"  coded_bytes {r['coded_bytes']}  coded_bpp {r['coded_bpp']:.4f}"
     return f"{name}: psnr {r['psnr']:.4f}  msssim {r['msssim']:.6f}  msssim_db {r['msssim_db']:.3f}{rate}"
 
 
@@ -105,15 +119,23 @@ def run(model, args) -> dict:
     image_paths = utils.read_image_list(args.data_list)
     sizes = [utils.image_size(p) for p in image_paths]
     rows = []
+    segment = None
+    if getattr(args, "entropy", "host") == "device":
+        if cum_freq is None:
+            raise ValueError(f"--entropy device needs the symbol distribution ({dist})")
+        segment = args.segment
     for group in ic.plan_batches(sizes, P, args.batch_images):
         images = [utils.imread(image_paths[i]) for i in group]
         for i, image, r in zip(group, images, ic.evaluate_images(images, post_filter=post is not None,
-                                                                 cum_freq=cum_freq)):
+                                                                 cum_freq=cum_freq, entropy_segment=segment)):
             H, W = image.shape[:2]
             row = {"path": image_paths[i], "height": H, "width": W, "sse": r["sse"], "psnr": r["psnr"],
                    "msssim": r["msssim"], "msssim_db": msssim_db(r["msssim"]), "n_symbols": r["n_symbols"],
                    "counts": [int(v) for v in r["counts"]], "est_bits": r["est_bits"],
                    "est_bpp": None if r["est_bits"] is None else r["est_bits"] / (H * W)}
+            if "coded_bytes" in r:
+                row["coded_bytes"] = r["coded_bytes"]
+                row["coded_bpp"] = 8.0 * r["coded_bytes"] / (H * W)
             rows.append(row)
             print(_line(image_paths[i], row))
     ic.close()

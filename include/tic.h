@@ -322,6 +322,66 @@ int tic_rc_decode(tic_rc_decoder* d, size_t n, const int64_t* cum_freq, size_t n
 int tic_rc_decoder_close(tic_rc_decoder* d);
 void tic_rc_decoder_free(tic_rc_decoder* d);
 
+/* --- segmented range-coder stream, version 1 (host part: no device) ---
+ * One container per symbol sequence, all integers little-endian:
+ *   0  4   magic "TICS"          8  4  L: symbols per segment (multiple of 4, 4..16384)
+ *   4  1   version = 1           12 8  n: symbols in the stream (> 0)
+ *   5  3   zero                  20 2*S u16 payload length of each segment, S = ceil(n / L)
+ *   then the S payloads back to back.
+ * Segment j holds symbols [j*L, min((j+1)*L, n)); its payload is exactly what
+ * tic_rc_encoder_open / tic_rc_encode / tic_rc_encoder_close write for those symbols (the minimal
+ * flush included; at most 3*len + 4 bytes) and decodes like that file (zeros past its end).
+ * Segments are independent streams, so the device entries below code one per lane.  Symbols are
+ * bytes: cum_freq as above with at most 257 entries and every frequency > 0.  Errors leave
+ * their message in tic_rc_last_error. */
+
+/* Worst-case container size: 20 + 2*S + 3*n + 4*S.  TIC_EINVAL for a bad L or n == 0. */
+int tic_rcseg_bound(size_t n, uint32_t L, size_t* bytes);
+/* Writes the container of sym[0..n) into out[0..cap) and its size into *written.  TIC_EINVAL for
+ * cap < tic_rcseg_bound, a bad table or a symbol outside it. */
+int tic_rcseg_encode(const uint8_t* sym, size_t n, uint32_t L, const int64_t* cum_freq, size_t ncum, uint8_t* out,
+                     size_t cap, size_t* written);
+/* Full validation: magic, version, reserved bytes, L, n > 0, the whole length table present,
+ * every length <= 3*len_j + 4, lengths summing to exactly the bytes that remain.  L / n may be
+ * NULL.  TIC_EINVAL otherwise. */
+int tic_rcseg_parse(const uint8_t* buf, size_t nbytes, uint32_t* L, uint64_t* n);
+/* tic_rcseg_parse, then TIC_EINVAL when n differs from the header's, then the n symbols. */
+int tic_rcseg_decode(const uint8_t* buf, size_t nbytes, const int64_t* cum_freq, size_t ncum, uint8_t* sym_out,
+                     size_t n);
+
+/* --- segmented streams on the device (csrc/tic_entropy.cpp) ---
+ * One range coder per lane, one segment each; a scan over the segment lengths; a gather that
+ * writes the containers.  All entries are asynchronous on the handle's stream, never synchronise,
+ * read their HOST arrays (offsets, counts, sizes) during the call only, and run on any handle.
+ * Deterministic: no atomic decides an output byte. */
+
+/* The table of the following calls on this handle (validated as the host entries do; replaces
+ * the previous one, ordered on the stream).  Totals up to 65536 decode through a value -> symbol
+ * table in LDS, larger ones (up to 2^24) through a search of the cumulative table. */
+int tic_entropy_set_table(tic_handle* h, const int64_t* cum_freq, size_t ncum);
+/* Device scratch (bytes) either device entry needs for streams of these symbol counts at segment
+ * length L (decode: the smallest L of the containers).  Host arithmetic only. */
+int tic_entropy_scratch_bytes(const int64_t* counts, int n_streams, uint32_t L, size_t* bytes);
+/* Stream i: counts[i] symbols at d_sym + sym_offsets[i] (any alignment, order, gaps).  d_out
+ * receives the n_streams containers back to back, d_sizes[i] (device, 8-byte aligned) their byte
+ * sizes; bytes behind the last container are not written.  A stream with a symbol outside the
+ * table gets d_sizes[i] = UINT64_MAX and contributes no bytes.  d_scratch 16-byte aligned.
+ * TIC_EINVAL with nothing launched for null pointers, a negative count or offset, counts[i] == 0,
+ * a bad L, no table, a scratch below tic_entropy_scratch_bytes or out_cap below the sum of
+ * tic_rcseg_bound; n_streams == 0 does nothing. */
+int tic_entropy_encode_device(tic_handle* h, const uint8_t* d_sym, const int64_t* sym_offsets, const int64_t* counts,
+                              int n_streams, uint32_t L, void* d_scratch, size_t scratch_bytes, uint8_t* d_out,
+                              size_t out_cap, uint64_t* d_sizes);
+/* Container i: blob_sizes[i] bytes at d_blob + blob_offsets[i], already passed through
+ * tic_rcseg_parse by the caller; its counts[i] symbols go to d_sym + sym_offsets[i].  Whatever
+ * the bytes hold, the kernels read only inside the container, clamp segment extents to it and
+ * write exactly counts[i] symbols below the table's symbol count (zeros for a container whose
+ * header does not fit counts[i], its size or the scratch); for a valid container they equal
+ * tic_rcseg_decode's. */
+int tic_entropy_decode_device(tic_handle* h, const uint8_t* d_blob, const int64_t* blob_offsets,
+                              const int64_t* blob_sizes, const int64_t* counts, int n_streams, uint8_t* d_sym,
+                              const int64_t* sym_offsets, void* d_scratch, size_t scratch_bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -92,6 +92,18 @@ SIGNATURES = [
     ("tic_rc_decode", C.c_int, [vp, C.c_size_t, C.POINTER(C.c_int64), C.c_size_t, C.POINTER(C.c_int64)]),
     ("tic_rc_decoder_close", C.c_int, [vp]),
     ("tic_rc_decoder_free", None, [vp]),
+    # segmented streams: host reference, then the device entries
+    ("tic_rcseg_bound", C.c_int, [C.c_size_t, C.c_uint32, C.POINTER(C.c_size_t)]),
+    ("tic_rcseg_encode", C.c_int, [u8p, C.c_size_t, C.c_uint32, C.POINTER(C.c_int64), C.c_size_t, u8p, C.c_size_t,
+                                  C.POINTER(C.c_size_t)]),
+    ("tic_rcseg_parse", C.c_int, [u8p, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+    ("tic_rcseg_decode", C.c_int, [u8p, C.c_size_t, C.POINTER(C.c_int64), C.c_size_t, u8p, C.c_size_t]),
+    ("tic_entropy_set_table", C.c_int, [vp, C.POINTER(C.c_int64), C.c_size_t]),
+    ("tic_entropy_scratch_bytes", C.c_int, [C.POINTER(C.c_int64), C.c_int, C.c_uint32, C.POINTER(C.c_size_t)]),
+    ("tic_entropy_encode_device", C.c_int, [vp, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int, C.c_uint32,
+                                           vp, C.c_size_t, vp, C.c_size_t, vp]),
+    ("tic_entropy_decode_device", C.c_int, [vp, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                           C.c_int, vp, C.POINTER(C.c_int64), vp, C.c_size_t]),
     ("tic_device_info", C.c_int, [vp, C.c_char_p, C.c_int]),
 ]
 

@@ -337,6 +337,59 @@ class Codec:
                                              ptr(ws, C.c_int32), off.size, d_scratch.ptr, d_scratch.nbytes,
                                              d_out.ptr), "tic_msssim_images_device")
 
+    # segmented range-coder streams on the device (tic_entropy.cpp; entropy.py is the host side)
+    @staticmethod
+    def _stream_table(*cols):
+        arrs = [np.ascontiguousarray(c, np.int64).reshape(-1) for c in cols]
+        if len({a.size for a in arrs}) != 1:
+            raise ValueError("per-stream arrays differ in length")
+        if arrs[0].size == 0:  # an empty array has no address to pass
+            arrs = [np.zeros(1, np.int64) for _ in arrs]
+            return 0, arrs
+        return arrs[0].size, arrs
+
+    def entropy_set_table(self, cum_freq) -> None:
+        """The cumulative table (``range_coder`` contract, at most 256 symbols, no zero frequency)
+        of the following entropy calls on this codec (tic_entropy_set_table)."""
+        from .range_coder import _table
+        t = _table(cum_freq)
+        check(lib().tic_entropy_set_table(self._h, ptr(t, C.c_int64), t.size), "tic_entropy_set_table")
+
+    @staticmethod
+    def entropy_scratch_bytes(counts, segment: int) -> int:
+        """Bytes of device scratch either entropy entry needs for streams of these symbol counts
+        (tic_entropy_scratch_bytes; for decoding, ``segment`` is the smallest L of the containers)."""
+        n, (cnt,) = Codec._stream_table(counts)
+        out = C.c_size_t()
+        check(lib().tic_entropy_scratch_bytes(ptr(cnt, C.c_int64), n, int(segment), C.byref(out)),
+              "tic_entropy_scratch_bytes")
+        return out.value
+
+    def entropy_encode_device(self, d_sym: DeviceBuffer, sym_offsets, counts, segment: int, d_scratch: DeviceBuffer,
+                              d_out: DeviceBuffer, d_sizes: DeviceBuffer, scratch_bytes: int | None = None,
+                              out_cap: int | None = None) -> None:
+        """Stream i (``counts[i]`` uint8 symbols at byte ``sym_offsets[i]`` of ``d_sym``) -> its
+        container; the containers back to back in ``d_out``, their sizes (uint64, UINT64_MAX for a
+        stream with a symbol outside the table) in ``d_sizes`` (tic_entropy_encode_device)."""
+        n, (off, cnt) = self._stream_table(sym_offsets, counts)
+        if d_sizes.nbytes < 8 * n:
+            raise ValueError(f"d_sizes holds {d_sizes.nbytes} bytes, {n} streams need {8 * n}")
+        check(lib().tic_entropy_encode_device(
+            self._h, d_sym.ptr, ptr(off, C.c_int64), ptr(cnt, C.c_int64), n, int(segment), d_scratch.ptr,
+            d_scratch.nbytes if scratch_bytes is None else int(scratch_bytes), d_out.ptr,
+            d_out.nbytes if out_cap is None else int(out_cap), d_sizes.ptr), "tic_entropy_encode_device")
+
+    def entropy_decode_device(self, d_blob: DeviceBuffer, blob_offsets, blob_sizes, counts, d_sym: DeviceBuffer,
+                              sym_offsets, d_scratch: DeviceBuffer, scratch_bytes: int | None = None) -> None:
+        """Container i (``blob_sizes[i]`` bytes at ``blob_offsets[i]`` of ``d_blob``, validated by
+        ``entropy.parse`` before the upload) -> its ``counts[i]`` symbols at ``sym_offsets[i]`` of
+        ``d_sym`` (tic_entropy_decode_device)."""
+        n, (boff, bsz, cnt, soff) = self._stream_table(blob_offsets, blob_sizes, counts, sym_offsets)
+        check(lib().tic_entropy_decode_device(
+            self._h, d_blob.ptr, ptr(boff, C.c_int64), ptr(bsz, C.c_int64), ptr(cnt, C.c_int64), n, d_sym.ptr,
+            ptr(soff, C.c_int64), d_scratch.ptr, d_scratch.nbytes if scratch_bytes is None else int(scratch_bytes)),
+            "tic_entropy_decode_device")
+
     def round_u8_device(self, d_in: DeviceBuffer, n: int, d_out: DeviceBuffer):
         check(lib().tic_round_u8_device(self._h, d_in.ptr, n, d_out.ptr), "tic_round_u8_device")
 

@@ -15,6 +15,7 @@
 // [0,0,0,0,1,2] x 17 = 136 bits) encodes to exactly 17 bytes of 0x0b.
 // The decoder reads zeros past the end of the file.  Several encode() calls (each with
 // its own table) append to one stream and are decoded by matching decode() calls.
+#include <algorithm>
 #include <cerrno>
 #include <cstdint>
 #include <cstdio>
@@ -50,16 +51,17 @@ int check_table(const int64_t* cum, size_t ncum, int64_t* total) {
   *total = cum[ncum - 1];
   return TIC_OK;
 }
-}  // namespace
 
-struct tic_rc_encoder {
-  FILE* f = nullptr;
+// The coder core, over any byte sink / source: the file API below and the segmented container
+// (tic_rcseg_*) run the same arithmetic, so a segment's payload is the file's bytes.
+template <class Sink>
+struct EncCore {
+  Sink s;
   uint64_t low = 0, range = kFull;
   int cache = -1;          // byte waiting for a possible carry (-1: none yet)
   uint64_t pending = 0;    // 0xFF bytes after the cache
-  bool closed = false;
 
-  bool put(int b) { return fputc(b, f) != EOF; }
+  bool put(int b) { return s.put(b); }
   bool emit_top() {  // move the top byte of the 32-bit window (bits 24..31) out of low
     if (low < 0xFF000000ull || low >= kFull) {
       const int carry = low >= kFull ? 1 : 0;
@@ -73,16 +75,126 @@ struct tic_rc_encoder {
     low = (low << 8) & (kFull - 1);
     return true;
   }
+  // one symbol [start, start + freq) of `total`; last: start + freq == total
+  bool symbol(uint64_t start, uint64_t freq, uint64_t total, bool last) {
+    const uint64_t r = range / total;
+    low += start * r;
+    range = last ? range - start * r : freq * r;
+    while (range < kTop) {
+      range <<= 8;
+      if (!emit_top()) return false;
+    }
+    return true;
+  }
+  // the minimal flush: fewest top bytes k of a value v in [low, low + range) whose remaining
+  // bytes are zero
+  bool finish() {
+    int k = 0;
+    uint64_t v = low;
+    for (; k <= 4; ++k) {
+      const int shift = 32 - 8 * k;
+      const uint64_t unit = shift >= 64 ? 0 : (1ull << shift);
+      v = k == 4 ? low : ((low + unit - 1) / unit) * unit;
+      if (v < low + range) break;
+    }
+    bool ok = true;
+    low = v;
+    for (int i = 0; i < k && ok; ++i) ok = emit_top();
+    if (ok && k > 0) {  // drain cache + pending (with the carry already folded in)
+      if (cache >= 0) ok = put(cache);
+      for (; ok && pending; --pending) ok = put(0xFF);
+    } else if (ok && cache >= 0) {
+      const int carry = v >= kFull ? 1 : 0;
+      ok = put((cache + carry) & 0xFF);
+      for (; ok && pending; --pending) ok = put((0xFF + carry) & 0xFF);
+    }
+    return ok;
+  }
 };
 
-struct tic_rc_decoder {
-  FILE* f = nullptr;
+template <class Source>
+struct DecCore {
+  Source s;
   uint64_t code = 0, range = kFull;
-  bool closed = false;
+  void start() {
+    for (int i = 0; i < 4; ++i) code = (code << 8) | (uint64_t)s.get();
+  }
+  int64_t symbol(const int64_t* cum, int64_t nsym, uint64_t total) {
+    const uint64_t r = range / total;
+    uint64_t val = code / r;
+    if (val >= total) val = total - 1;
+    // last s with cum[s] <= val (and freq > 0)
+    int64_t lo = 0, hi = nsym - 1;
+    while (lo < hi) {
+      const int64_t mid = (lo + hi + 1) / 2;
+      if ((uint64_t)cum[mid] <= val) lo = mid;
+      else hi = mid - 1;
+    }
+    const uint64_t start = (uint64_t)cum[lo];
+    code -= start * r;
+    range = ((uint64_t)cum[lo + 1] == total) ? range - start * r : (uint64_t)(cum[lo + 1] - cum[lo]) * r;
+    while (range < kTop) {
+      range <<= 8;
+      code = ((code << 8) | (uint64_t)s.get()) & (kFull - 1);
+    }
+    return lo;
+  }
+};
+
+struct FileSink {
+  FILE* f = nullptr;
+  bool put(int b) { return fputc(b, f) != EOF; }
+};
+struct FileSource {
+  FILE* f = nullptr;
   int get() {
     const int c = fgetc(f);
     return c == EOF ? 0 : c;
   }
+};
+struct MemSink {  // the caller guarantees room (tic_rcseg_bound)
+  uint8_t* p = nullptr;
+  bool put(int b) {
+    *p++ = (uint8_t)b;
+    return true;
+  }
+};
+struct MemSource {  // bytes past the end read as zero
+  const uint8_t *p = nullptr, *end = nullptr;
+  int get() { return p < end ? *p++ : 0; }
+};
+
+// --- segmented stream, version 1 (include/tic.h) ---
+constexpr uint32_t kSegMaxL = 16384;
+constexpr size_t kSegHeader = 20;
+const uint8_t kSegMagic[4] = {'T', 'I', 'C', 'S'};
+
+bool seg_L_ok(uint32_t L) { return L >= 4 && L <= kSegMaxL && L % 4 == 0; }
+uint32_t rd32(const uint8_t* p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
+uint64_t rd64(const uint8_t* p) { return (uint64_t)rd32(p) | (uint64_t)rd32(p + 4) << 32; }
+void wr32(uint8_t* p, uint32_t v) {
+  for (int i = 0; i < 4; ++i) p[i] = (uint8_t)(v >> (8 * i));
+}
+
+// check_table plus the byte-symbol contract: at most 256 symbols, every frequency > 0
+int check_seg_table(const int64_t* cum, size_t ncum, int64_t* total) {
+  int rc = check_table(cum, ncum, total);
+  if (rc) return rc;
+  if (ncum > 257) return rc_fail(TIC_EINVAL, "segmented streams code byte symbols: at most 257 table entries");
+  for (size_t i = 1; i < ncum; ++i)
+    if (cum[i] == cum[i - 1]) return rc_fail(TIC_EINVAL, "segmented streams need every frequency > 0");
+  return TIC_OK;
+}
+}  // namespace
+
+struct tic_rc_encoder {
+  EncCore<FileSink> c;
+  bool closed = false;
+};
+
+struct tic_rc_decoder {
+  DecCore<FileSource> c;
+  bool closed = false;
 };
 
 extern "C" {
@@ -94,7 +206,7 @@ int tic_rc_encoder_open(const char* path, tic_rc_encoder** out) {
   FILE* f = fopen(path, "wb");
   if (!f) return rc_fail(TIC_EIO, std::string("cannot open ") + path + ": " + strerror(errno));
   *out = new tic_rc_encoder();
-  (*out)->f = f;
+  (*out)->c.s.f = f;
   return TIC_OK;
 }
 
@@ -110,13 +222,7 @@ int tic_rc_encode(tic_rc_encoder* e, const int64_t* data, size_t n, const int64_
     if (s < 0 || s >= nsym) return rc_fail(TIC_EINVAL, "symbol " + std::to_string(s) + " outside the table (cumFreq too short)");
     const uint64_t start = (uint64_t)cum[s], freq = (uint64_t)(cum[s + 1] - cum[s]);
     if (freq == 0) return rc_fail(TIC_EINVAL, "symbols with zero probability cannot be encoded");
-    const uint64_t r = e->range / (uint64_t)total;
-    e->low += start * r;
-    e->range = (cum[s + 1] == total) ? e->range - start * r : freq * r;
-    while (e->range < kTop) {
-      e->range <<= 8;
-      if (!e->emit_top()) return rc_fail(TIC_EIO, "write failed");
-    }
+    if (!e->c.symbol(start, freq, (uint64_t)total, cum[s + 1] == total)) return rc_fail(TIC_EIO, "write failed");
   }
   return TIC_OK;
 }
@@ -125,34 +231,15 @@ int tic_rc_encoder_close(tic_rc_encoder* e) {
   if (!e) return rc_fail(TIC_EINVAL, "null encoder");
   if (e->closed) return TIC_OK;
   e->closed = true;
-  // fewest top bytes k of a value v in [low, low + range) whose remaining bytes are zero
-  int k = 0;
-  uint64_t v = e->low;
-  for (; k <= 4; ++k) {
-    const int shift = 32 - 8 * k;
-    const uint64_t unit = shift >= 64 ? 0 : (1ull << shift);
-    v = k == 4 ? e->low : ((e->low + unit - 1) / unit) * unit;
-    if (v < e->low + e->range) break;
-  }
-  bool ok = true;
-  e->low = v;
-  for (int i = 0; i < k && ok; ++i) ok = e->emit_top();
-  if (ok && k > 0) {  // drain cache + pending (with the carry already folded in)
-    if (e->cache >= 0) ok = e->put(e->cache);
-    for (; ok && e->pending; --e->pending) ok = e->put(0xFF);
-  } else if (ok && e->cache >= 0) {
-    const int carry = v >= kFull ? 1 : 0;
-    ok = e->put((e->cache + carry) & 0xFF);
-    for (; ok && e->pending; --e->pending) ok = e->put((0xFF + carry) & 0xFF);
-  }
-  if (fclose(e->f) != 0) ok = false;
-  e->f = nullptr;
+  bool ok = e->c.finish();
+  if (fclose(e->c.s.f) != 0) ok = false;
+  e->c.s.f = nullptr;
   return ok ? TIC_OK : rc_fail(TIC_EIO, "write failed");
 }
 
 void tic_rc_encoder_free(tic_rc_encoder* e) {
   if (!e) return;
-  if (e->f) fclose(e->f);
+  if (e->c.s.f) fclose(e->c.s.f);
   delete e;
 }
 
@@ -161,8 +248,8 @@ int tic_rc_decoder_open(const char* path, tic_rc_decoder** out) {
   FILE* f = fopen(path, "rb");
   if (!f) return rc_fail(TIC_EIO, std::string("cannot open ") + path + ": " + strerror(errno));
   tic_rc_decoder* d = new tic_rc_decoder();
-  d->f = f;
-  for (int i = 0; i < 4; ++i) d->code = (d->code << 8) | (uint64_t)d->get();
+  d->c.s.f = f;
+  d->c.start();
   *out = d;
   return TIC_OK;
 }
@@ -174,41 +261,132 @@ int tic_rc_decode(tic_rc_decoder* d, size_t n, const int64_t* cum, size_t ncum, 
   int rc = check_table(cum, ncum, &total);
   if (rc) return rc;
   const int64_t nsym = (int64_t)ncum - 1;
-  for (size_t i = 0; i < n; ++i) {
-    const uint64_t r = d->range / (uint64_t)total;
-    uint64_t val = d->code / r;
-    if (val >= (uint64_t)total) val = (uint64_t)total - 1;
-    // last s with cum[s] <= val (and freq > 0)
-    int64_t lo = 0, hi = nsym - 1;
-    while (lo < hi) {
-      const int64_t mid = (lo + hi + 1) / 2;
-      if ((uint64_t)cum[mid] <= val) lo = mid;
-      else hi = mid - 1;
-    }
-    const uint64_t start = (uint64_t)cum[lo];
-    d->code -= start * r;
-    d->range = (cum[lo + 1] == total) ? d->range - start * r : (uint64_t)(cum[lo + 1] - cum[lo]) * r;
-    out[i] = lo;
-    while (d->range < kTop) {
-      d->range <<= 8;
-      d->code = ((d->code << 8) | (uint64_t)d->get()) & (kFull - 1);
-    }
-  }
+  for (size_t i = 0; i < n; ++i) out[i] = d->c.symbol(cum, nsym, (uint64_t)total);
   return TIC_OK;
 }
 
 int tic_rc_decoder_close(tic_rc_decoder* d) {
   if (!d) return rc_fail(TIC_EINVAL, "null decoder");
-  if (!d->closed && d->f) fclose(d->f);
-  d->f = nullptr;
+  if (!d->closed && d->c.s.f) fclose(d->c.s.f);
+  d->c.s.f = nullptr;
   d->closed = true;
   return TIC_OK;
 }
 
 void tic_rc_decoder_free(tic_rc_decoder* d) {
   if (!d) return;
-  if (d->f) fclose(d->f);
+  if (d->c.s.f) fclose(d->c.s.f);
   delete d;
 }
 
+// --- segmented stream ---
+
+int tic_rcseg_bound(size_t n, uint32_t L, size_t* bytes) {
+  if (!bytes) return rc_fail(TIC_EINVAL, "null argument");
+  *bytes = 0;
+  if (!seg_L_ok(L)) return rc_fail(TIC_EINVAL, "segment length " + std::to_string(L) + " must be a multiple of 4 in [4, 16384]");
+  if (n == 0) return rc_fail(TIC_EINVAL, "a segmented stream holds at least one symbol");
+  if (n > (SIZE_MAX >> 3)) return rc_fail(TIC_EINVAL, "too many symbols");
+  const size_t S = (n + L - 1) / L;
+  *bytes = kSegHeader + 2 * S + 3 * n + 4 * S;
+  return TIC_OK;
+}
+
+int tic_rcseg_encode(const uint8_t* sym, size_t n, uint32_t L, const int64_t* cum, size_t ncum, uint8_t* out,
+                     size_t cap, size_t* written) {
+  if (!sym || !out || !written) return rc_fail(TIC_EINVAL, "null argument");
+  *written = 0;
+  size_t bound = 0;
+  int rc = tic_rcseg_bound(n, L, &bound);
+  if (rc) return rc;
+  int64_t total = 0;
+  if ((rc = check_seg_table(cum, ncum, &total))) return rc;
+  if (cap < bound)
+    return rc_fail(TIC_EINVAL, "output of " + std::to_string(cap) + " bytes is below tic_rcseg_bound (" + std::to_string(bound) + ")");
+  const size_t S = (n + L - 1) / L, nsym = ncum - 1;
+  memcpy(out, kSegMagic, 4);
+  wr32(out + 4, 1);  // version 1, three zero bytes
+  wr32(out + 8, L);
+  wr32(out + 12, (uint32_t)((uint64_t)n & 0xFFFFFFFFu));
+  wr32(out + 16, (uint32_t)((uint64_t)n >> 32));
+  uint8_t* lens = out + kSegHeader;
+  uint8_t* p = lens + 2 * S;
+  for (size_t j = 0; j < S; ++j) {
+    const size_t b = j * L, e = std::min(n, b + L);
+    EncCore<MemSink> c;
+    c.s.p = p;
+    for (size_t i = b; i < e; ++i) {
+      const size_t s = sym[i];
+      if (s >= nsym) return rc_fail(TIC_EINVAL, "symbol " + std::to_string(s) + " outside the table (cumFreq too short)");
+      c.symbol((uint64_t)cum[s], (uint64_t)(cum[s + 1] - cum[s]), (uint64_t)total, cum[s + 1] == total);
+    }
+    c.finish();
+    const size_t len = (size_t)(c.s.p - p);
+    lens[2 * j] = (uint8_t)(len & 0xFF);
+    lens[2 * j + 1] = (uint8_t)(len >> 8);
+    p = c.s.p;
+  }
+  *written = (size_t)(p - out);
+  return TIC_OK;
+}
+
+int tic_rcseg_parse(const uint8_t* buf, size_t nbytes, uint32_t* L_out, uint64_t* n_out) {
+  if (!buf) return rc_fail(TIC_EINVAL, "null argument");
+  if (nbytes < kSegHeader) return rc_fail(TIC_EINVAL, "not a segmented stream: shorter than its 20-byte header");
+  if (memcmp(buf, kSegMagic, 4) != 0) return rc_fail(TIC_EINVAL, "not a segmented stream: magic is not \"TICS\"");
+  if (buf[4] != 1) return rc_fail(TIC_EINVAL, "segmented stream version " + std::to_string(buf[4]) + " is not supported");
+  if (buf[5] || buf[6] || buf[7]) return rc_fail(TIC_EINVAL, "segmented stream: reserved bytes are not zero");
+  const uint32_t L = rd32(buf + 8);
+  const uint64_t n = rd64(buf + 12);
+  if (!seg_L_ok(L)) return rc_fail(TIC_EINVAL, "segmented stream: segment length " + std::to_string(L) + " must be a multiple of 4 in [4, 16384]");
+  if (n == 0) return rc_fail(TIC_EINVAL, "segmented stream: no symbols");
+  const uint64_t rest = nbytes - kSegHeader;
+  if (n > (UINT64_MAX >> 3) || (n + L - 1) / L > rest / 2)
+    return rc_fail(TIC_EINVAL, "segmented stream: truncated inside the length table");
+  const uint64_t S = (n + L - 1) / L;
+  const uint8_t* lens = buf + kSegHeader;
+  uint64_t sum = 0;
+  for (uint64_t j = 0; j < S; ++j) {
+    const uint64_t len = (uint64_t)lens[2 * j] | (uint64_t)lens[2 * j + 1] << 8;
+    const uint64_t cnt = j + 1 < S ? L : n - j * L;
+    if (len > 3 * cnt + 4)
+      return rc_fail(TIC_EINVAL, "segmented stream: segment " + std::to_string(j) + " claims " + std::to_string(len) +
+                                     " bytes for " + std::to_string(cnt) + " symbols");
+    sum += len;
+  }
+  if (sum != rest - 2 * S)
+    return rc_fail(TIC_EINVAL, "segmented stream: segment lengths sum to " + std::to_string(sum) + " bytes, " +
+                                   std::to_string(rest - 2 * S) + " follow the length table");
+  if (L_out) *L_out = L;
+  if (n_out) *n_out = n;
+  return TIC_OK;
+}
+
+int tic_rcseg_decode(const uint8_t* buf, size_t nbytes, const int64_t* cum, size_t ncum, uint8_t* sym_out, size_t n) {
+  if (!sym_out) return rc_fail(TIC_EINVAL, "null argument");
+  uint32_t L = 0;
+  uint64_t hn = 0;
+  int rc = tic_rcseg_parse(buf, nbytes, &L, &hn);
+  if (rc) return rc;
+  if (hn != (uint64_t)n)
+    return rc_fail(TIC_EINVAL, "segmented stream holds " + std::to_string(hn) + " symbols, " + std::to_string(n) + " expected");
+  int64_t total = 0;
+  if ((rc = check_seg_table(cum, ncum, &total))) return rc;
+  const size_t S = (n + L - 1) / L;
+  const uint8_t* lens = buf + kSegHeader;
+  const uint8_t* p = lens + 2 * S;
+  for (size_t j = 0; j < S; ++j) {
+    const size_t len = (size_t)lens[2 * j] | (size_t)lens[2 * j + 1] << 8;
+    const size_t b = j * L, e = std::min(n, b + L);
+    DecCore<MemSource> c;
+    c.s.p = p;
+    c.s.end = p + len;
+    c.start();
+    for (size_t i = b; i < e; ++i) sym_out[i] = (uint8_t)c.symbol(cum, (int64_t)ncum - 1, (uint64_t)total);
+    p += len;
+  }
+  return TIC_OK;
+}
+
 }  // extern "C"
+

@@ -314,8 +314,90 @@ class ImageCodec:
         flat = d_out.download((total,), np.uint8)
         return [flat[o:o + H * W * 3].reshape(H, W, 3).copy() for o, (H, W) in zip(offsets, sizes)]
 
+    # ------------------------------------------------------------------ segmented streams
+    # The entropy coder on the device (tic_entropy.cpp): the symbols of a group never visit the
+    # host, every image becomes one "TICS" container (entropy.py), all of them in one coder call.
+    def _entropy_encode(self, d_sym: DeviceBuffer, counts, cum_freq, segment: int):
+        """Symbols of consecutive streams in ``d_sym`` -> (d_blob, d_sizes), nothing downloaded."""
+        c = self.codec
+        c.entropy_set_table(cum_freq)
+        offs = np.concatenate([[0], np.cumsum(counts)[:-1]]).astype(np.int64)
+        d_scr = self._buf("entropy_scratch", c.entropy_scratch_bytes(counts, segment))
+        from . import entropy
+        d_blob = self._buf("entropy_blob", sum(entropy.bound(n, segment) for n in counts))
+        d_sizes = self._buf("entropy_sizes", 8 * len(counts))
+        c.entropy_encode_device(d_sym, offs, counts, segment, d_scr, d_blob, d_sizes)
+        return d_blob, d_sizes
+
+    def encode_images_to_streams(self, images, cum_freq, segment: int = 2048) -> list[bytes]:
+        """[uint8 [H_i, W_i, 3]] -> one segmented-stream container per image (entropy.unpack gives
+        ``encode_images``' symbols back): one upload, ``encode_images_device``, one coder call over
+        all images, one download of the sizes and one of the containers."""
+        imgs = [np.ascontiguousarray(im) for im in images]
+        for im in imgs:
+            if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3 or im.size == 0:
+                raise ValueError(f"image must be uint8 [H, W, 3], got {im.dtype} {im.shape}")
+        if not imgs:
+            return []
+        sizes = [im.shape[:2] for im in imgs]
+        offsets, total = self.packed_offsets(sizes)
+        code = int(np.prod(self.codec.code_shape))
+        counts = [self.num_patches(H, W) * code for H, W in sizes]
+        d_img = self._buf("image_u8", total)
+        d_img.upload(np.concatenate([im.reshape(-1) for im in imgs]))
+        d_sym = self._buf("symbols", sum(counts))
+        self.encode_images_device(d_img, offsets, sizes, d_sym)
+        d_blob, d_sizes = self._entropy_encode(d_sym, counts, cum_freq, segment)
+        nbytes = d_sizes.download((len(imgs),), np.uint64)
+        bad = np.flatnonzero(nbytes == np.iinfo(np.uint64).max)
+        if bad.size:
+            raise ValueError(f"image {int(bad[0])}: a symbol outside the frequency table")
+        blob = d_blob.download((int(nbytes.sum()),), np.uint8)
+        cuts = np.cumsum(nbytes.astype(np.int64))[:-1]
+        return [part.tobytes() for part in np.split(blob, cuts)]
+
+    def decode_streams_to_images(self, streams, sizes, cum_freq, post_filter: bool = True) -> list[np.ndarray]:
+        """[container], [(H_i, W_i)] -> [uint8 [H_i, W_i, 3]]: every container is validated on the
+        host (entropy.parse) and its symbol count checked against the image size and the code
+        shape; then one upload, one decoder call for all of them and ``decode_images_device``."""
+        from . import entropy
+        sizes = [(int(H), int(W)) for H, W in sizes]
+        if len(streams) != len(sizes):
+            raise ValueError(f"{len(streams)} streams for {len(sizes)} image sizes")
+        if not sizes:
+            return []
+        c = self.codec
+        code = int(np.prod(c.code_shape))
+        counts, min_L = [], 16384
+        for i, (buf, (H, W)) in enumerate(zip(streams, sizes)):
+            if H <= 0 or W <= 0:
+                raise ValueError(f"image size {H}x{W} must be positive")
+            L, n = entropy.parse(buf)
+            want = self.num_patches(H, W) * code
+            if n != want:
+                raise ValueError(f"stream {i} holds {n} symbols, a {H}x{W} image has {want}")
+            counts.append(n)
+            min_L = min(min_L, L)
+        blob = np.frombuffer(b"".join(bytes(b) for b in streams), np.uint8)
+        bsizes = [len(b) for b in streams]
+        boffs = np.concatenate([[0], np.cumsum(bsizes)[:-1]]).astype(np.int64)
+        soffs = np.concatenate([[0], np.cumsum(counts)[:-1]]).astype(np.int64)
+        c.entropy_set_table(cum_freq)
+        d_blob = self._buf("entropy_blob", blob.size)
+        d_blob.upload(blob)
+        d_scr = self._buf("entropy_scratch", c.entropy_scratch_bytes(counts, min_L))
+        d_sym = self._buf("symbols", sum(counts))
+        c.entropy_decode_device(d_blob, boffs, bsizes, counts, d_sym, soffs, d_scr)
+        offsets, total = self.packed_offsets(sizes)
+        d_out = self._buf("image_out", total)
+        self.decode_images_device(d_sym, offsets, sizes, d_out, post_filter)
+        self.synchronize()
+        flat = d_out.download((total,), np.uint8)
+        return [flat[o:o + H * W * 3].reshape(H, W, 3).copy() for o, (H, W) in zip(offsets, sizes)]
+
     # ------------------------------------------------------------------ rate / distortion
-    def evaluate_images(self, images, post_filter: bool = True, cum_freq=None) -> list[dict]:
+    def evaluate_images(self, images, post_filter: bool = True, cum_freq=None,
+                        entropy_segment: int | None = None) -> list[dict]:
         """Round trip of a list of uint8 [H_i, W_i, 3] images with its quality and rate measures,
         without leaving the device: one upload, ``encode_images_device`` / ``decode_images_device``
         on one arena, per image the exact squared error (tic_sse_u8_device) and the symbol
@@ -324,7 +406,10 @@ class ImageCodec:
         the small results.  Per image: ``sse`` (int), ``psnr`` (evaluate.mse2psnr of sse / dims),
         ``msssim``, ``counts`` (uint64 [Q]), ``n_symbols`` and ``est_bits``
         (evaluate.estimated_bits under ``cum_freq``, a range_coder.symbol_table table; None
-        without one).  Images start at 4-byte boundaries of the arena (the alignment
+        without one).  With ``entropy_segment`` and ``cum_freq`` every result also has
+        ``coded_bytes``: the size of the image's segmented-stream container at that segment length,
+        from one entropy_encode_device call over the symbols on the device (the real rate beside
+        the estimate).  Images start at 4-byte boundaries of the arena (the alignment
         tic_sse_u8_device asks for)."""
         from . import evaluate as ev
         imgs = [np.ascontiguousarray(im) for im in images]
@@ -353,6 +438,9 @@ class ImageCodec:
         d_sym = self._buf("symbols", int(pbase[-1]) * code)
         d_out = self._buf("image_out", total)
         self.encode_images_device(d_img, offsets, sizes, d_sym)
+        d_sizes = None
+        if entropy_segment is not None and cum_freq is not None:
+            _, d_sizes = self._entropy_encode(d_sym, [k * code for k in counts], cum_freq, int(entropy_segment))
         self.decode_images_device(d_sym, offsets, sizes, d_out, post_filter)
         if post_filter and self.post is not None:
             c.wait_event(self.post, self.last_slot)  # d_out was written on the post-filter's stream
@@ -371,6 +459,9 @@ class ImageCodec:
         ints = raw[:n * rec].view(np.uint64).reshape(n, 1 + Q)
         sums = raw[n * rec:].view(np.float64).reshape(len(big), 5, 3, 2)
         ms = {i: ev.msssim_from_sums(sums[k], *sizes[i]) for k, i in enumerate(big)}
+        coded = None if d_sizes is None else d_sizes.download((n,), np.uint64)
+        if coded is not None and np.any(coded == np.iinfo(np.uint64).max):
+            raise ValueError("a symbol outside the frequency table")
         out = []
         for i, (H, W) in enumerate(sizes):
             sse = int(ints[i, 0])
@@ -380,6 +471,8 @@ class ImageCodec:
             out.append({"sse": sse, "psnr": psnr, "msssim": ms.get(i, float("nan")), "counts": cnt,
                         "n_symbols": counts[i] * code,
                         "est_bits": None if cum_freq is None else ev.estimated_bits(cnt, cum_freq)})
+            if coded is not None:
+                out[-1]["coded_bytes"] = int(coded[i])
         return out
 
     def close(self) -> None:
