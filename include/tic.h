@@ -113,7 +113,10 @@ int tic_rmbe_device(tic_handle* h, const float* d_windows, int n, float* d_out);
  * (1 or 2), "chain_x" (1: the encoder's stride-2 layer in front of a run and the decoder's
  * transposed layer behind it run inside the chain's launch; 2: also the decoder's next
  * transposed layer (decode_2); needs chain_wh 2; default 1 for models 0-2, the shipped tuning
- * decides), "chain_order" (region placement: 0 atomic ticket, 1 blockIdx, 2 a
+ * decides), "chain_j" (tic_codec_device only: the encoder's last chain launch — head, run,
+ * quantiser — and the decoder's first — dequantiser, run, tail — as one launch, where both are
+ * planned on the same stage with chain_x; tic_encode_device / tic_decode_device keep their
+ * launches; default 1 for models 0-2, env TIC_CHAIN_J), "chain_order" (region placement: 0 atomic ticket, 1 blockIdx, 2 a
  * patch's regions on one XCD, -1 automatic), "s1_form" (stride-1 form: 0 direct, 1 Winograd F(2x2,3x3), 2 Winograd F(4x4,3x3)
  * for the 64->64 res-block convs, other layers falling back to 1; -1 the model's default: 2 for
  * model_3 and the rmbe net, 1 otherwise; env TIC_S1_FORM=direct|wino|wino4), "s2_form" (standalone
@@ -161,6 +164,10 @@ int tic_layer_variant(const tic_handle* h, int i, int n, int* th, int* nsplit);
  * form tools/pmc_summary.py prints (e.g. "conv3x3<1,32,32,4,4,1,false,1,false,0,0>");
  * empty when the layer runs inside the previous layer's launch.  cap includes the NUL. */
 int tic_layer_kernel(const tic_handle* h, int i, int n, char* name, int cap);
+/* The same for the launches of tic_codec_device.  They are tic_layer_kernel's except where
+ * option "chain_j" joins the encoder's last and the decoder's first chain launch: the joined
+ * launch is named at its first layer (HT bit 16 set) and every other layer of it is empty. */
+int tic_codec_kernel(const tic_handle* h, int i, int n, char* name, int cap);
 /* Tuning state as text (every tuned tiling / variant per layer and batch key, and the
  * structural fusion flags), so a tuning run can be replayed exactly by another process of
  * the same build (like cuDNN's find-db): returns the length (excluding the NUL) and writes

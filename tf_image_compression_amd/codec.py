@@ -248,6 +248,16 @@ class Codec:
             out.append(buf.value.decode())
         return out
 
+    def codec_kernels(self, n: int):
+        """Kernel instance each layer launches in codec_device for batch n: layer_kernels' except
+        where option "chain_j" joins the two chain launches at the quantiser (tic_codec_kernel)."""
+        out = []
+        for i in range(len(self.layers())):
+            buf = C.create_string_buffer(160)
+            check(lib().tic_codec_kernel(self._h, i, n, buf, 160), "tic_codec_kernel")
+            out.append(buf.value.decode())
+        return out
+
     def tuning_export(self) -> str:
         """Tuned tilings / variants / fusion flags as text (tic_tuning_export)."""
         n = check(lib().tic_tuning_export(self._h, None, 0), "tic_tuning_export")

@@ -494,6 +494,8 @@ struct tic_handle {
                            // 1 the encoder's stride-2 layer in front as the head, the decoder's
                            // transposed layer behind as the tail; 2 also the decoder's next
                            // transposed layer (decode_2) behind the tail; wino_chain.h HT)
+  int chain_j = 0;         // the codec step's encoder-side and decoder-side chain launches as one
+                           // (option "chain_j": wino_chain.h CH_JOIN; chain_join_at)
   int chain_order = -1;    // chain region order (option "chain_order"): 0 atomic ticket, 1 blockIdx,
                            // 2 blockIdx XCD-aware, -1 auto: 2 when every lane's chain grid is
                            // resident at once, else 0 (chain_launch_order)
@@ -726,13 +728,15 @@ const int kRgbInDefault = 2;   // TH 16
 // rmbe net (the step tuner keeps it off there), and with it the stride-2 head / transposed tail
 // ("chain_x", env TIC_CHAIN_X: model_0 step -3.1 % in alternating A/B, profiles/
 // ab_r05_chain_x_m0.json).
+// "chain_j" (env TIC_CHAIN_J): tic_codec_device's encoder-side and decoder-side chain launches
+// joined at the quantiser, where the chain runs with its head and tail.
 struct StructDefaults {
   bool fuse01, fuse_tail, chain;
-  int chain_x;
+  int chain_x, chain_j;
 };
 StructDefaults struct_defaults(int model_id) {
   const bool small_stages = model_id == 0 || model_id == 1 || model_id == 2;
-  return {true, true, small_stages, small_stages ? 1 : 0};
+  return {true, true, small_stages, small_stages ? 1 : 0, small_stages ? 1 : 0};
 }
 
 // Stride-1 form policy (like the last layer's): TIC_S1_FORM=direct|wino|wino4, else built-in:
@@ -827,7 +831,7 @@ static int chain_end(const tic_handle* h, int li) {
   const bool first_dec = !h->rmbe() && li == h->n_enc;
   if (!first_dec && s1_64(li - 1) && (h->rmbe() || li - 1 != h->n_enc - 1)) return li;  // not a run start
   int j = li + 1;
-  while (j < L - 1 && j - li < tic::CH_MAX_LAYERS && s1_64(j) && (h->rmbe() || j != h->n_enc)) ++j;
+  while (j < L - 1 && j - li < tic::CH_MAX_RUN && s1_64(j) && (h->rmbe() || j != h->n_enc)) ++j;
   {
     // Geometry the region chain can run: a region keeps its workgroup for all nl
     // layers, and to publish layer k region t needs layer k-1 of region t + rw + 1, which needs
@@ -849,7 +853,7 @@ static int chain_end(const tic_handle* h, int li) {
     j = std::min(j, li + atoi(t));
     return j - li >= 2 ? j : li;
   }
-  // A run cut short (residency above, or CH_MAX_LAYERS) never ends inside a res_block: the
+  // A run cut short (residency above, or CH_MAX_RUN) never ends inside a res_block: the
   // chain keeps a block input it read in LDS only, so the block's residual conv must run in
   // the same launch (after a run, the per-layer path has no block input in a workspace)
   while (j - li >= 2 && h->layers[j].def.residual) --j;
@@ -942,6 +946,35 @@ static bool any_chain_x(const tic_handle* h, int level = 1) {
   return false;
 }
 
+// The codec step's joined launch (option "chain_j", wino_chain.h CH_JOIN): the chain launch that
+// starts at layer li is the encoder's last one (head, run, quantiser) and the decoder's first
+// one (dequantiser, run, tail, perhaps decode_2) follows it on the same stage — both have the
+// same grid, tiles and hand-off protocol, and only the region's own symbols cross between them,
+// so a pass over both network halves (tic_codec_device) runs them as one launch of
+// enc run + dec run layers.  *dec = the decoder-side span.  A region still waits on regions of
+// its own patch only, so the residency argument is chain_x_fits' (every region of a patch
+// resident in every lane), whatever the number of layers.  The caller leaves the join out when
+// per-layer events are recorded or the handle is inside per-layer tuning.
+static bool chain_join_at(const tic_handle* h, int li, ChainSpan* dec) {
+  if (!h->chain_j || h->rmbe() || h->chain_wh != 2) return false;
+  const ChainSpan sp = chain_span_at(h, li);
+  if (!sp.valid() || !sp.head || sp.tail || sp.end != h->n_enc) return false;
+  const ChainSpan d = chain_span_at(h, h->n_enc);
+  if (!d.valid() || d.start != h->n_enc || d.head || !d.tail) return false;
+  const int hw = h->layers[sp.s1].h_in;
+  if (h->layers[d.s1].h_in != hw || !chain_x_fits(h, hw)) return false;
+  if ((sp.end - sp.s1) + (d.end - d.s1) > tic::CH_MAX_LAYERS) return false;
+  *dec = d;
+  return true;
+}
+// the layer at which tic_codec_device's joined launch starts, or -1 when it runs two launches
+static int codec_join_start(const tic_handle* h) {
+  ChainSpan d;
+  for (const ChainSpan& sp : chain_spans(h))
+    if (sp.end == h->n_enc && chain_join_at(h, sp.start, &d)) return sp.start;
+  return -1;
+}
+
 // Whether stride-2 / transposed layer i may run the polyphase Winograd form (s2_form 1): only
 // where no fused kernel could run it under the handle's form policies — encode_1 (enc01),
 // decode_1 (dec10), and with the chain's stride-1 form (1) a chain's stride-2 head and
@@ -980,7 +1013,9 @@ bool pwino_layer(const tic_handle* h, int i) {
 }
 
 // Run layers [l0, l1) for n patches. Input: `in` (u8 patches, f32 windows or u8 symbols);
-// outputs per-position flags.  Buffers rotate through h->ws.
+// outputs per-position flags.  Buffers rotate through h->ws.  A pass over both halves of a
+// codec ([0, L): tic_codec_device) reads the decoder's symbols from d_idx, and runs the
+// encoder's last and the decoder's first chain launch as one where chain_join_at plans it.
 static constexpr int kMarkCap = 1024;  // event pairs per lane
 
 int run_layers(tic_handle* h, Lane& ln, int l0, int l1, const void* in, int n, uint8_t* d_idx, float* d_pre,
@@ -994,6 +1029,8 @@ int run_layers(tic_handle* h, Lane& ln, int l0, int l1, const void* in, int n, u
   // whose launch is left out, to price a group of layers inside the whole step
   unsigned long long probe_skip = 0;
   if (const char* s = getenv("TIC_PROBE_SKIP")) probe_skip = strtoull(s, nullptr, 0);
+  // the decoder's input: the symbols this same pass wrote, or the caller's
+  const void* const sym_in = !h->rmbe() && l0 < h->n_enc && l1 > h->n_enc ? (const void*)d_idx : in;
   int marked = -1;  // event pair open around the launch of layer mark_layer
   auto mark_close = [&]() -> int {
     if (marked >= 0) {
@@ -1116,21 +1153,27 @@ int run_layers(tic_handle* h, Lane& ln, int l0, int l1, const void* in, int n, u
       break;
     }
     const ChainSpan sp = chain_span_at(h, li);
+    ChainSpan jd;  // the decoder-side launch joined to this one (tic_codec_device's pass)
+    const bool join = sp.valid() && !prof.ev && h->tune_reps == 0 && chain_join_at(h, li, &jd) && jd.last() < l1;
     if (sp.valid() && sp.last() < l1) {
-      const int s1 = sp.s1, ce = sp.end, nl = ce - s1;
+      const int s1 = sp.s1, ce = sp.end, nl = ce - s1 + (join ? jd.end - jd.s1 : 0);
+      const ChainSpan& tsp = join ? jd : sp;  // the span that carries the tail
+      const int te = tsp.end;                 // the tail's layer
       const LayerRT& lr = h->layers[s1];  // the run's first stride-1 layer
       const bool first_dec_c = !h->rmbe() && s1 == h->n_enc;
       const bool last_enc_c = !h->rmbe() && ce - 1 == h->n_enc - 1;
       const int R = ((lr.h_in + 7) / 8) * ((lr.h_in + 7) / 8);  // 8x8 regions per patch
-      int rc = ensure_chain(h, ln, nl + (sp.head ? 1 : 0) + (sp.tail ? 1 : 0), n, R);  // hand-offs + 1
+      // hand-offs + 1 (joined: the junction is one more slot of the same protocol)
+      int rc = ensure_chain(h, ln, nl + (sp.head ? 1 : 0) + (tsp.tail ? 1 : 0), n, R);
       if (rc) return rc;
       tic::ChainArgs a{};
-      for (int k = 0; k < nl; ++k) {
+      for (int k = 0; k < nl; ++k) {  // (joined: the decoder's run follows the encoder's, s1 + k)
         const LayerRT& lk = h->layers[s1 + k];
         a.layer[k] = {lk.d_ww, lk.d_b, lk.def.act, lk.def.residual};
       }
       a.nl = nl;
-      a.in = first_dec_c ? in : (const void*)src;
+      a.nq = join ? ce - s1 - 1 : -1;
+      a.in = first_dec_c ? sym_in : (const void*)src;
       a.lut = h->d_lut;
       a.out = last_enc_c ? d_pre : ws[dst];
       a.qout = last_enc_c ? d_idx : nullptr;
@@ -1148,40 +1191,41 @@ int run_layers(tic_handle* h, Lane& ln, int l0, int l1, const void* in, int n, u
         a.hH = a.hW = lay.h_in;
         a.hpad = same_pad(K_S2, lay.h_in);
       }
-      if (sp.tail) {  // the transposed layer behind (layer ce), writing the next activation
-        const LayerRT& tl = h->layers[ce];
+      if (tsp.tail) {  // the transposed layer behind (layer te), writing the next activation
+        const LayerRT& tl = h->layers[te];
         a.tail = {tl.d_w, tl.d_b, tl.def.act, 0};
         a.tail_out = ws[dst];
       }
-      const bool tail2_pw = sp.tail2 && layer_form(h, h->layers[ce + 1]) == 1;
-      if (sp.tail2) {  // and the next one (decode_2), whose output is the next activation instead;
+      const bool tail2_pw = tsp.tail2 && layer_form(h, h->layers[te + 1]) == 1;
+      if (tsp.tail2) {  // and the next one (decode_2), whose output is the next activation instead;
                        // in its polyphase Winograd form where the s2_form policy runs it so
-        const LayerRT& tl2 = h->layers[ce + 1];
+        const LayerRT& tl2 = h->layers[te + 1];
         a.tail2 = {tail2_pw ? tl2.d_wp : tl2.d_w, tl2.d_b, tl2.def.act, 0};
         a.tail2_out = ws[dst];
       }
       if (const char* pr = getenv("TIC_CHAIN_PROBE")) a.probe = atoi(pr);
       if (getenv("TIC_CHAIN_TIMING")) {  // phase timestamps of this launch (tools/chain_timing.py)
-        int rc2 = probe_stamps(ln, first_dec_c || sp.tail ? 1 : 0, n * R, st, &a.tstamp);
+        int rc2 = probe_stamps(ln, first_dec_c || tsp.tail ? 1 : 0, n * R, st, &a.tstamp);
         if (rc2) return rc2;
       }
       const int inm = first_dec_c ? tic::IN_IDX : tic::IN_F32, outm = last_enc_c ? tic::OUT_QUANT : tic::OUT_F32;
-      const int ht = (sp.head ? tic::CH_HEAD : 0) | (sp.tail ? tic::CH_TAIL : 0) | (sp.tail2 ? tic::CH_TAIL2 : 0) |
-                     (tail2_pw ? tic::CH_TAIL2_PW : 0);
+      const int ht = (sp.head ? tic::CH_HEAD : 0) | (tsp.tail ? tic::CH_TAIL : 0) | (tsp.tail2 ? tic::CH_TAIL2 : 0) |
+                     (tail2_pw ? tic::CH_TAIL2_PW : 0) | (join ? tic::CH_JOIN : 0);
+      const int span_last = tsp.last();
       if (!tic::launch_wino_chain(inm, outm, a, st, h->chain_wh, ht))
-        return fail(TIC_EUNSUPPORTED, "no chain kernel for layers %d..%d", li, sp.last());
+        return fail(TIC_EUNSUPPORTED, "no chain kernel for layers %d..%d", li, span_last);
       rc = check_launch();
       if (rc) return rc;
       if (prof.ev) {
         HIP_TRY(hipEventRecord(prof.ev[2 * li + 1], st));
-        for (int k = li + 1; k <= sp.last(); ++k) {  // the other layers ran inside this launch
+        for (int k = li + 1; k <= span_last; ++k) {  // the other layers ran inside this launch
           HIP_TRY(hipEventRecord(prof.ev[2 * k], st));
           HIP_TRY(hipEventRecord(prof.ev[2 * k + 1], st));
         }
       }
       block_in = -1;
       cur = dst;
-      li = sp.last();
+      li = span_last;
       continue;
     }
     if (first) {
@@ -1249,7 +1293,7 @@ int run_layers(tic_handle* h, Lane& ln, int l0, int l1, const void* in, int n, u
         return fail(TIC_EUNSUPPORTED, "no kernel for layer %s (kind %d %d->%d act %d res %d in %d out %d)",
                     d.name.c_str(), d.kind, d.cin, d.cout, d.act, d.residual, inm, outm);
       tic::ConvArgs a{};
-      a.in = first_dec ? in : (const void*)src;
+      a.in = first_dec ? sym_in : (const void*)src;
       a.wp = lay.d_w;
       a.bias = lay.d_b;
       if (d.residual && block_in < 0)  // (a chain run ending inside a res_block: never planned)
@@ -1428,10 +1472,15 @@ int decode_dev(tic_handle* h, const uint8_t* idx, int n, uint8_t* rgb, float* f3
 int codec_dev(tic_handle* h, const uint8_t* in, int n, uint8_t* idx, uint8_t* rgb) {
   const size_t pp = (size_t)h->P * h->P * 3, ce = code_elems(h);
   const PatchBuf bufs[3] = {{in, pp, false}, {idx, ce, true}, {rgb, pp, true}};
+  const bool joined = h->tune_reps == 0 && codec_join_start(h) >= 0;
   for (int s = 0; s < n; s += h->chunk) {
     const int m = std::min(h->chunk, n - s);
     int rc = run_chunk(h, s, m, h->tune_reps == 0, bufs, 3, [&](Lane& ln, int o, int k) {
       const int b = s + o;
+      // the joined launch spans the bottleneck: one pass over both halves
+      if (joined)
+        return run_layers(h, ln, 0, (int)h->layers.size(), in + b * pp, k, idx + b * ce, nullptr, rgb + b * pp, nullptr,
+                          Prof{nullptr});
       int r = run_layers(h, ln, 0, h->n_enc, in + b * pp, k, idx + b * ce, nullptr, nullptr, nullptr, Prof{nullptr});
       if (r) return r;
       return run_layers(h, ln, h->n_enc, (int)h->layers.size(), idx + b * ce, k, nullptr, nullptr, rgb + b * pp,
@@ -1549,12 +1598,14 @@ int tic_create(int model_id, int patch_size, int quan_scale, int device, tic_han
     h->fuse_tail = sd.fuse_tail;
     h->chain = sd.chain;
     h->chain_x = sd.chain_x;
+    h->chain_j = sd.chain_j;
   }
   if (const char* f = getenv("TIC_FUSE01")) h->fuse01 = atoi(f) != 0;
   if (const char* f = getenv("TIC_FUSE_TAIL")) h->fuse_tail = atoi(f) != 0;
   if (const char* f = getenv("TIC_CHAIN")) h->chain = atoi(f) != 0;
   if (const char* f = getenv("TIC_CHAIN_WH")) h->chain_wh = std::min(2, std::max(1, atoi(f)));
   if (const char* f = getenv("TIC_CHAIN_X")) h->chain_x = std::min(2, std::max(0, atoi(f)));
+  if (const char* f = getenv("TIC_CHAIN_J")) h->chain_j = atoi(f) != 0;
   if (const char* f = getenv("TIC_CHAIN_ORDER")) h->chain_order = std::min(2, std::max(-1, atoi(f)));
   if (const char* f = getenv("TIC_DECOUPLE")) h->decouple = atoi(f) != 0;
   hipError_t e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
@@ -1995,6 +2046,13 @@ int tic_set_option(tic_handle* h, const char* key, int value) {
     h->chain_x = value < 0 ? struct_defaults(h->model_id).chain_x : value;
     return TIC_OK;
   }
+  if (k == "chain_j") {  // tic_codec_device: the encoder's and the decoder's chain launch as one (-1: default)
+    if (value < -1 || value > 1) return fail(TIC_EINVAL, "chain_j must be -1, 0 or 1");
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    clear_graphs(h);
+    h->chain_j = value < 0 ? struct_defaults(h->model_id).chain_j : value;
+    return TIC_OK;
+  }
   if (k == "chain_order") {  // 0 atomic ticket, 1 blockIdx, 2 blockIdx XCD-aware, -1 auto
     if (value < -1 || value > 2) return fail(TIC_EINVAL, "chain_order must be -1, 0, 1 or 2");
     HIP_TRY(hipStreamSynchronize(h->stream));
@@ -2406,6 +2464,20 @@ int tic_autotune_step(tic_handle* h, const void* d_in, int n, int rounds, int re
       clear_graphs(h);
     }
   }
+  if (!rc && h->chain && !getenv("TIC_CHAIN_J")) {  // the two chain launches of the step joined at the quantiser
+    const int was = h->chain_j;
+    h->chain_j = 1;
+    const bool can = codec_join_start(h) >= 0;
+    h->chain_j = was;
+    if (can && t_flip) {
+      h->chain_j = !was;
+      clear_graphs(h);
+    } else if (can) {
+      bool keep = false;
+      rc = confirm([&](bool alt) { h->chain_j = alt ? !was : was; }, kStructMargin, "chain_j", &keep, &cur);
+      clear_graphs(h);
+    }
+  }
   const int L = (int)h->layers.size();
   for (int round = 0; round < rounds && !rc; ++round) {
     for (int i = 0; i < L && !rc; ++i) {
@@ -2624,6 +2696,24 @@ int tic_layer_kernel(const tic_handle* h, int i, int n, char* name, int cap) {
   return TIC_OK;
 }
 
+int tic_codec_kernel(const tic_handle* h, int i, int n, char* name, int cap) {
+  if (!h || !name || cap <= 0) return fail(TIC_EINVAL, "null argument");
+  if (i < 0 || i >= (int)h->layers.size()) return fail(TIC_EINVAL, "layer index %d out of range", i);
+  const int js = h->tune_reps == 0 ? codec_join_start(h) : -1;
+  ChainSpan jd;
+  if (js < 0 || !chain_join_at(h, js, &jd) || i < js || i > jd.last()) return tic_layer_kernel(h, i, n, name, cap);
+  char buf[160] = "";  // layers inside the joined launch: empty, as inside any fused launch
+  if (i == js) {
+    const int ht = tic::CH_HEAD | tic::CH_JOIN | tic::CH_TAIL | (jd.tail2 ? tic::CH_TAIL2 : 0) |
+                   (jd.tail2 && layer_form(h, h->layers[jd.end + 1]) == 1 ? tic::CH_TAIL2_PW : 0);
+    snprintf(buf, sizeof buf, "wino_chain_kernel<0,1,%d,%d>", h->chain_wh, ht);
+  }
+  const int len = (int)strlen(buf);
+  if (len + 1 > cap) return fail(TIC_EINVAL, "name buffer too small (%d < %d)", cap, len + 1);
+  memcpy(name, buf, len + 1);
+  return TIC_OK;
+}
+
 int tic_tuning_export(const tic_handle* h, char* buf, int cap) {
   if (!h || (!buf && cap > 0)) return fail(TIC_EINVAL, "null argument");
   const tic::ConvEntry* (*regs[3])(int*) = {tic::conv_registry_s1, tic::conv_registry_s2,
@@ -2636,6 +2726,7 @@ int tic_tuning_export(const tic_handle* h, char* buf, int cap) {
   t += "flag chain " + std::to_string((int)h->chain) + "\n";
   t += "flag chain_wh " + std::to_string(h->chain_wh) + "\n";
   t += "flag chain_x " + std::to_string((int)h->chain_x) + "\n";
+  t += "flag chain_j " + std::to_string((int)h->chain_j) + "\n";
   for (size_t i = 0; i < h->layers.size(); ++i) {
     const LayerRT& l = h->layers[i];
     for (const auto& kv : l.tuned) {
@@ -2660,6 +2751,10 @@ int tic_tuning_import(tic_handle* h, const char* text) {
   std::vector<std::map<int, int>> vars(L);
   int fuse01 = h->fuse01, fuse_tail = h->fuse_tail, s1_form = h->s1_form, chain = h->chain, chain_wh = h->chain_wh;
   int chain_x = h->chain_x, s2_form = h->s2_form;
+  // chain_j: a state exported before the flag existed (flag lines, none of them chain_j) takes
+  // the model's default; a text of entries only leaves it, like every other flag, as it is
+  int chain_j = -1;
+  bool any_flag = false;
   const char* p = text;
   int line = 0;
   while (*p) {
@@ -2676,6 +2771,7 @@ int tic_tuning_import(tic_handle* h, const char* text) {
       return fail(TIC_EINVAL, "tuning text line %d: unreadable", line);
     } else if (!strcmp(kind, "flag")) {
       if (sscanf(ln.c_str(), "flag %31s %d", name, &a) != 2) return fail(TIC_EINVAL, "tuning line %d", line);
+      any_flag = true;
       if (!strcmp(name, "fuse01")) fuse01 = a != 0;
       else if (!strcmp(name, "fuse_tail")) fuse_tail = a != 0;
       else if (!strcmp(name, "s1_form") && a >= 0 && a <= 2) s1_form = a;
@@ -2683,6 +2779,7 @@ int tic_tuning_import(tic_handle* h, const char* text) {
       else if (!strcmp(name, "chain")) chain = a != 0;
       else if (!strcmp(name, "chain_wh") && a >= 1 && a <= 2) chain_wh = a;
       else if (!strcmp(name, "chain_x") && a >= 0 && a <= 2) chain_x = a;
+      else if (!strcmp(name, "chain_j") && a >= 0 && a <= 1) chain_j = a;
       else return fail(TIC_EINVAL, "tuning line %d: unknown flag %s", line, name);
     } else if (!strcmp(kind, "conv")) {
       if (sscanf(ln.c_str(), "conv %d %d %d %d", &a, &b, &c, &d) != 4 || a < 0 || a >= L || c < 0 || c > 2)
@@ -2697,7 +2794,26 @@ int tic_tuning_import(tic_handle* h, const char* text) {
           ce->res != ld.residual || ce->in != (first_dec ? tic::IN_IDX : tic::IN_F32) ||
           ce->out != (last_enc ? tic::OUT_QUANT : tic::OUT_F32))
         return fail(TIC_EINVAL, "tuning line %d: kernel does not match layer %s", line, ld.name.c_str());
+      // the form is a policy, never a tuning outcome: the entry's form is its key's
+      // (ADVICE r06): entry_form(*ce) must be the form in the key, b >> 24 — or, for a signature
+      // that form has no instance of, the form it falls back to (form_fallback), which is what
+      // the tuner itself stores under that key
       const int hg = ld.kind == K_T2 ? h->layers[a].h_in : h->layers[a].h_out;
+      {
+        const int kf = b >> 24;
+        int want = -1;
+        for (int pass = 0; pass < 3 && want < 0 && kf >= 0 && kf <= 2; ++pass) {
+          const int fm = form_fallback(kf, pass);
+          if (fm < 0) break;
+          for (int i = 0; i < cnt && want < 0; ++i)
+            if (base[i].cin == ce->cin && base[i].cout == ce->cout && base[i].act == ce->act && base[i].res == ce->res &&
+                base[i].in == ce->in && base[i].out == ce->out && entry_form(base[i]) == fm && wino4_fits(base[i], hg, hg))
+              want = fm;
+        }
+        if (entry_form(*ce) != want)
+          return fail(TIC_EINVAL, "tuning line %d: kernel form %d under a form-%d key (layer %s)", line,
+                      entry_form(*ce), kf, ld.name.c_str());
+      }
       if (!wino4_fits(*ce, hg, hg))
         return fail(TIC_EINVAL, "tuning line %d: the F(4x4,3x3) form cannot run layer %s at this patch size", line,
                     ld.name.c_str());
@@ -2732,6 +2848,7 @@ int tic_tuning_import(tic_handle* h, const char* text) {
   h->chain = chain;
   h->chain_wh = chain_wh;
   h->chain_x = chain_x;
+  h->chain_j = chain_j >= 0 ? chain_j : any_flag ? struct_defaults(h->model_id).chain_j : h->chain_j;
   return TIC_OK;
 }
 

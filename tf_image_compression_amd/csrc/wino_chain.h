@@ -52,7 +52,9 @@
 
 namespace tic {
 
-constexpr int CH_MAX_LAYERS = 8;
+// Winograd layers in one launch: a joined launch (CH_JOIN) holds the encoder's and the decoder's
+// run (5 + 5 for models 0-2); a run of one network half stays within CH_MAX_RUN
+constexpr int CH_MAX_LAYERS = 12, CH_MAX_RUN = 8;
 // timestamps per workgroup: kernel start, input staged, then per layer: start, K loop done,
 // epilogue done, border published, neighbours' flags seen, halo staged; then the head's six
 // (window staged, K loop done, epilogue done, published, flags seen, halo staged) and the
@@ -67,6 +69,11 @@ constexpr int CH_END_TS = CH_W4_TAIL + 3, CH_TS = CH_END_TS + 1;
 constexpr int CH_HEAD = 1, CH_TAIL = 2, CH_TAIL2 = 4;  // HT bits (CH_TAIL2 needs CH_TAIL)
 // decode_2 behind the tail in the polyphase Winograd form (s2_form 1; needs CH_TAIL2)
 constexpr int CH_TAIL2_PW = 8;
+// the encoder's run and the decoder's run in one launch (needs CH_HEAD and CH_TAIL): run layer
+// ChainArgs::nq is the encoder's last one — its epilogue quantises (OUT_QUANT's arithmetic, the
+// symbols to qout) and hands the dequantised symbols on as the next layer's input, which is
+// what the decoder-side launch stages from qout through the table
+constexpr int CH_JOIN = 16;
 
 struct ChainLayer {
   const float* wu;    // Winograd U [16 p][4 kc][4 g][64][4 t] (pack_wino)
@@ -78,10 +85,12 @@ struct ChainLayer {
 struct ChainArgs {
   ChainLayer layer[CH_MAX_LAYERS];
   int nl;               // layers in the chain (2..CH_MAX_LAYERS)
+  int nq;               // HT & CH_JOIN: the run layer that feeds the quantiser (0 <= nq < nl - 1)
   const void* in;       // first layer's input: f32 [n,H,W,64] or u8 symbols (IN_IDX)
-  const float* lut;     // IN_IDX: dequantiser table
-  float* out;           // last layer: f32 [n,H,W,64] (OUT_F32) / optional pre-activation (OUT_QUANT)
-  uint8_t* qout;        // OUT_QUANT: u8 symbols [n,H,W,64]
+  const float* lut;     // IN_IDX / CH_JOIN: dequantiser table (256 floats)
+  float* out;           // last layer: f32 [n,H,W,64] (OUT_F32) / optional pre-activation (OUT_QUANT;
+                        // CH_JOIN: of layer nq)
+  uint8_t* qout;        // OUT_QUANT: u8 symbols [n,H,W,64] (CH_JOIN: layer nq's)
   float qscale;         // Q - 1
   int H, W;             // spatial size of every layer (stride 1)
   int rh, rw;           // 8x8 regions per patch: ceil(H/8) x ceil(W/8)
@@ -195,7 +204,9 @@ __global__ void __launch_bounds__(256 * WH, WH == 1 ? 2 : 1) wino_chain_kernel(c
   using namespace chain;
   constexpr int NTH = 256 * WH;
   constexpr bool HEAD = (HT & CH_HEAD) != 0, TAIL = (HT & CH_TAIL) != 0, TAIL2 = (HT & CH_TAIL2) != 0;
-  constexpr bool TAIL2_PW = (HT & CH_TAIL2_PW) != 0;
+  constexpr bool TAIL2_PW = (HT & CH_TAIL2_PW) != 0, JOIN = (HT & CH_JOIN) != 0;
+  static_assert(!JOIN || (HEAD && TAIL && IN == IN_F32 && OUT == OUT_QUANT),
+                "a joined launch runs from the encoder's head through the quantiser to the decoder's tail");
   static_assert(!TAIL2_PW || TAIL2, "the polyphase decode_2 is the one behind the tail");
   static_assert(!TAIL2 || TAIL, "decode_2 runs on the tail's output");
   static_assert(HT == 0 || WH == 2, "stride-2 head / tail: 512-thread workgroups only");
@@ -210,6 +221,7 @@ __global__ void __launch_bounds__(256 * WH, WH == 1 ? 2 : 1) wino_chain_kernel(c
   constexpr int SMEM = HEAD && TILE + HWIN > SM0 ? TILE + HWIN : SM0;
   __shared__ __attribute__((aligned(16))) float smem[SMEM];
   __shared__ __attribute__((aligned(16))) float sbias[CH_MAX_LAYERS * C];
+  __shared__ float slut[JOIN ? 256 : 1];  // CH_JOIN: the dequantiser table
   __shared__ unsigned sh[2];
   const int tid = threadIdx.x;
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -232,6 +244,9 @@ __global__ void __launch_bounds__(256 * WH, WH == 1 ? 2 : 1) wino_chain_kernel(c
   }
   // every layer's bias, read by the epilogues from LDS
   for (int e = tid; e < a.nl * C; e += NTH) sbias[e] = a.layer[e / C].bias[e % C];
+  if constexpr (JOIN) {
+    if (tid < 256) slut[tid] = a.lut[tid];
+  }
   __syncthreads();
   const int ticket = (int)sh[0];
   const unsigned epoch = sh[1] + 1u;  // this launch's flag value
@@ -683,6 +698,29 @@ __global__ void __launch_bounds__(256 * WH, WH == 1 ? 2 : 1) wino_chain_kernel(c
         }
       stamp(ts + 2);
       break;
+    }
+
+    if constexpr (JOIN) {
+      // ---- the junction: layer nq is the encoder's last one.  OUT_QUANT's epilogue (the same
+      // symbols and pre-activations at the same addresses), then the dequantised symbols go on
+      // as the next layer's input — the floats the decoder-side launch stages from qout ----
+      if (l == a.nq) {
+#pragma unroll
+        for (int k = 0; k < nay; ++k)
+#pragma unroll
+          for (int b = 0; b < 2; ++b) {
+            const int oy = oy0 + 2 * ety + ay0 + k, ox = ox0 + 2 * etx + b;
+            const f32x4 v = y[k][b];
+            const uint32_t q0 = quant1(v.x, a.qscale), q1 = quant1(v.y, a.qscale), q2 = quant1(v.z, a.qscale),
+                           q3 = quant1(v.w, a.qscale);
+            if (oy < H && ox < W) {
+              const size_t o = ((size_t)(nimg * H + oy) * W + ox) * C + co;
+              if (a.out) *reinterpret_cast<f32x4*>(a.out + o) = v;
+              *reinterpret_cast<uint32_t*>(a.qout + o) = q0 | (q1 << 8) | (q2 << 16) | (q3 << 24);
+            }
+            y[k][b] = f32x4{slut[q0 & 0xff], slut[q1 & 0xff], slut[q2 & 0xff], slut[q3 & 0xff]};
+          }
+      }
     }
 
     // ---- into the next layer's (TAIL: the tail's) tile, zero outside the image; a border

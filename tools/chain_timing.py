@@ -35,15 +35,19 @@ def read_dumps(path):
     return out
 
 
-def summarise(t, nl):
+def summarise(t):
     us = lambda a: a.astype(np.float64) / 100.0  # 100 MHz ticks -> us
     t = t.astype(np.int64)
+    # wino_chain.h: CH_TS = 19 + 7 CH_MAX_LAYERS stamps per workgroup; the layers that ran left
+    # their start stamps (5 in an encoder- or decoder-side launch of model_0, 10 in the joined one)
+    ml = (t.shape[1] - 19) // 7
+    nl = max(1, sum(1 for l in range(ml) if np.all(t[:, 2 + 6 * l] != 0)))
     start = t[:, 0]
     rep = {"workgroups": int(t.shape[0]),
            "start_spread_us": round(float(us(start.max() - start.min())), 2),
            "stage_us": round(float(np.median(us(t[:, 1] - t[:, 0]))), 2),
            "kernel_us": round(float(us(t[:, 2 + 6 * (nl - 1) + 2].max() - start.min())), 2),
-           "layers": []}
+           "layers_run": nl, "layers": []}
     for l in range(nl):
         b = 2 + 6 * l
         row = {}
@@ -54,7 +58,7 @@ def summarise(t, nl):
         rep["layers"].append(row)
     # the stride-2 head / transposed tail of a chain_x launch (wino_chain.h CH_HEAD_TS / CH_TAIL_TS:
     # stamps after the 8 layer slots)
-    hb = 2 + 6 * 8
+    hb = 2 + 6 * ml
     if t.shape[1] >= hb + 12:
         if np.all(t[:, hb + 5] != 0):
             marks = [0] + [hb + k for k in range(6)]
@@ -75,24 +79,24 @@ def summarise(t, nl):
     # workgroup's end (wino_chain.h CH_W4_TS .. CH_END_TS): "w4_lag" = how much later wave 4
     # finishes a K loop than wave 0, i.e. how much of thread 0's next phase is its wait for it
     w4 = hb + 12
-    if t.shape[1] >= w4 + 13:
+    if t.shape[1] >= w4 + ml + 5:
         med = lambda d: [round(float(np.median(us(d))), 2), round(float(np.percentile(us(d), 90)), 2)]
         lag = {}
         for l in range(nl):
             if np.all(t[:, w4 + l] != 0):
                 lag[f"layer{l}"] = med(t[:, w4 + l] - t[:, 2 + 6 * l + 1])
-        if np.all(t[:, w4 + 8] != 0) and np.all(t[:, hb + 1] != 0):
-            lag["head"] = med(t[:, w4 + 8] - t[:, hb + 1])
+        if np.all(t[:, w4 + ml] != 0) and np.all(t[:, hb + 1] != 0):
+            lag["head"] = med(t[:, w4 + ml] - t[:, hb + 1])
         tb = hb + 6
-        if np.all(t[:, w4 + 9] != 0):
-            lag["tail"] = med(t[:, w4 + 9] - t[:, tb + 1])
-        if np.all(t[:, w4 + 10] != 0):
-            lag["d2"] = med(t[:, w4 + 10] - t[:, tb + 3])
-            rep["w4_d2_store"] = med(t[:, w4 + 11] - t[:, w4 + 10])
+        if np.all(t[:, w4 + ml + 1] != 0):
+            lag["tail"] = med(t[:, w4 + ml + 1] - t[:, tb + 1])
+        if np.all(t[:, w4 + ml + 2] != 0):
+            lag["d2"] = med(t[:, w4 + ml + 2] - t[:, tb + 3])
+            rep["w4_d2_store"] = med(t[:, w4 + ml + 3] - t[:, w4 + ml + 2])
         rep["w4_lag"] = lag
-        if np.all(t[:, w4 + 12] != 0):
-            rep["wg_life_us"] = med(t[:, w4 + 12] - start)
-            rep["kernel_us"] = round(float(us(t[:, w4 + 12].max() - start.min())), 2)
+        if np.all(t[:, w4 + ml + 4] != 0):
+            rep["wg_life_us"] = med(t[:, w4 + ml + 4] - start)
+            rep["kernel_us"] = round(float(us(t[:, w4 + ml + 4].max() - start.min())), 2)
     return rep
 
 
@@ -123,6 +127,7 @@ def main():
     ap.add_argument("--enc01", action="store_true")
     ap.add_argument("--chain-wh", type=int, default=0, help="chain workgroup shape (option chain_wh), 0: the tuning's")
     ap.add_argument("--chain-x", type=int, default=-1, help="option chain_x (stride-2 head / tail), -1: the tuning's")
+    ap.add_argument("--chain-j", type=int, default=-1, help="option chain_j (the two chain launches joined), -1: the tuning's")
     args = ap.parse_args()
     path = os.path.join(tempfile.mkdtemp(), "chain_ts.bin")
     os.environ["TIC_ENC01_TIMING" if args.enc01 else "TIC_CHAIN_TIMING"] = path
@@ -141,6 +146,8 @@ def main():
             c.set_option("chain_wh", args.chain_wh)
         if args.chain_x >= 0:
             c.set_option("chain_x", args.chain_x)
+        if args.chain_j >= 0:
+            c.set_option("chain_j", args.chain_j)
     eh, ew, ec = bottleneck_shape(M, P)
     x = np.random.default_rng(1234).integers(0, 256, (B, P, P, 3), dtype=np.uint8)
     d_in, d_idx, d_rgb = c.alloc(x.nbytes), c.alloc(B * eh * ew * ec), c.alloc(x.nbytes)
@@ -149,15 +156,15 @@ def main():
         c.codec_device(d_in, B, d_idx, d_rgb)
     c.synchronize()  # dumps the last launch of every lane and side
     dumps = read_dumps(path)
-    nl = 5
     for lane, slot, t in dumps:
         if slot == 2:
             rep = summarise_enc01(t)
             rep.update({"lane": lane, "kernel": "enc01"})
             print(json.dumps(rep), flush=True)
             continue
-        rep = summarise(t, nl)
-        rep.update({"lane": lane, "side": "decoder" if slot else "encoder"})
+        rep = summarise(t)
+        joined = rep["layers_run"] > 8  # more layers than one half's run: the codec step's joined launch
+        rep.update({"lane": lane, "side": "joined" if joined else "decoder" if slot else "encoder"})
         print(json.dumps(rep), flush=True)
     c.close()
 
