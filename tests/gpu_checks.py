@@ -58,6 +58,236 @@ def check_codec_subset(codec, params, model_id, P, patches, k, Q=2):
     return idx, rgb
 
 
+# ---------------------------------------------------------------------------
+# Crafted parameters and inputs of the quantiser / dequantiser / unclipped-decoder tests
+# (test_gpu_quantiser.py, test_gpu_dequantiser.py; their input conditions are asserted on the
+# CPU by test_parity_inputs_host.py).  Nothing below needs a GPU.
+# ---------------------------------------------------------------------------
+
+QUANT_QS = (2, 3, 4, 6, 16, 255, 256)
+# the clamp and expf's overflow: sigmoid saturates in f32 from |x| ~ 17 on, expf(x) is inf from
+# x ~ 88.7 on and expf(-x) flushes to 0 from x ~ 104 on
+QUANT_EXTREMES = (20.0, 88.0, 89.0, 104.0, 1e4, 3e38)
+
+
+def last_encoder_layer(model_id):
+    return o.MODELS[model_id][0][-1][0]
+
+
+def first_decoder_layer(model_id):
+    return o.MODELS[model_id][1][0][0]
+
+
+def last_decoder_layer(model_id):
+    return o.MODELS[model_id][1][-1][0]
+
+
+def quantize_f64(x, Q):
+    """oracle.quantize without the overflow warning of exp(1e4)."""
+    with np.errstate(over="ignore"):
+        return o.quantize(np.asarray(x, np.float64), Q)
+
+
+def quant_level_f64(x, Q):
+    """sigmoid(x) * (Q - 1) in float64: the real number the quantiser rounds."""
+    with np.errstate(over="ignore"):
+        return 1.0 / (1.0 + np.exp(-np.asarray(x, np.float64))) * (Q - 1)
+
+
+def half_margin(t):
+    """Distance of a level t from the nearest half-integer (a rounding threshold)."""
+    return np.abs(t - np.floor(t) - 0.5)
+
+
+def quant_bias_vector(Q, cout):
+    """(b, tie): cout float32 pre-activations whose symbol is known, and which of them are the
+    exact tie.  +-0 (sigmoid = 0.5 exactly, level (Q-1)/2: a tie for even Q); the clamp / overflow
+    values +-QUANT_EXTREMES; and for levels k spread evenly over 0..Q-2 (k = 0 and k = Q-2
+    always) the two points a quarter level inside the thresholds of k + 0.5:
+    float32(logit((k + 0.5 -+ 0.25) / (Q-1))).  Ordered so that neighbouring channels have
+    different symbols wherever the symbols allow it (a lane or byte permutation of the packed
+    store then changes the result); a list shorter than cout repeats."""
+    q1 = Q - 1
+    vals = [0.0, -0.0]
+    for v in QUANT_EXTREMES:
+        vals += [v, -v]
+    nk = max(1, min(q1, (cout - len(vals)) // 2))
+    for k in sorted({int(round(k)) for k in np.linspace(0, Q - 2, nk)}):
+        for d in (0.25, 0.75):
+            p = (k + d) / q1
+            vals.append(float(np.float32(np.log(p / (1.0 - p)))))
+    vals = np.asarray(vals, np.float32)
+    sym = quantize_f64(vals, Q)
+    order, rest = [], list(range(len(vals)))
+    while rest:
+        recent = [sym[i] for i in order[-3:]]
+        pick = next((i for i in rest if sym[i] not in recent), None)
+        if pick is None:
+            pick = next((i for i in rest if not order or sym[i] != sym[order[-1]]), rest[0])
+        order.append(pick)
+        rest.remove(pick)
+    b = np.asarray([vals[order[j % len(order)]] for j in range(cout)], np.float32)
+    return b, b == 0
+
+
+def quantiser_params(model_id, b, seed=0):
+    """synthetic params whose last encoder layer has a zero kernel and bias b: every
+    pre-activation is b[c] exactly in every form (Winograd transforms of zeros are zeros)."""
+    from tf_image_compression_amd.weights import synthetic_params
+    params = dict(synthetic_params(model_id, seed=seed))
+    name = last_encoder_layer(model_id)
+    params[f"{name}/kernel"] = np.zeros_like(params[f"{name}/kernel"])
+    params[f"{name}/bias"] = np.asarray(b, np.float32)
+    assert params[f"{name}/bias"].shape == (params[f"{name}/kernel"].shape[3],)
+    return params
+
+
+def gained_params(model_id, gain, seed=0):
+    """synthetic params with the last encoder layer's kernel and bias multiplied by gain (at
+    gain 4, model_0's pre-activations reach every one of 256 levels)."""
+    from tf_image_compression_amd.weights import synthetic_params
+    params = dict(synthetic_params(model_id, seed=seed))
+    name = last_encoder_layer(model_id)
+    for v in ("kernel", "bias"):
+        params[f"{name}/{v}"] = (params[f"{name}/{v}"] * np.float32(gain)).astype(np.float32)
+    return params
+
+
+# the last decoder layer's kernel gain that keeps the reconstruction inside (0, 255)
+UNCLIPPED_GAIN = {0: 1 / 8, 1: 1 / 4, 2: 1 / 8, 3: 1 / 32, 128: 1 / 32}
+# (model, P): every model at the smallest patch size the suite runs it at
+UNCLIPPED_CASES = [(0, 64), (1, 32), (2, 32), (3, 64), (128, 64)]
+
+
+def unclipped_params(model_id, seed=0):
+    """synthetic params with the last decoder layer's kernel scaled by UNCLIPPED_GAIN (bias
+    unchanged): with the plain synthetic weights up to 85 % of the oracle's outputs are exactly 0
+    or 255 and the float and byte bars see nothing of the last layers there."""
+    from tf_image_compression_amd.weights import synthetic_params
+    params = dict(synthetic_params(model_id, seed=seed))
+    name = last_decoder_layer(model_id)
+    params[f"{name}/kernel"] = (params[f"{name}/kernel"] * np.float32(UNCLIPPED_GAIN[model_id])).astype(np.float32)
+    return params
+
+
+def clipped_share_and_span(ref_f):
+    f = np.asarray(ref_f)
+    return float(np.mean((f <= 0) | (f >= 255))), float(f.max() - f.min())
+
+
+def quant_rule_excluded(pre, Q):
+    """(t, safe): the f64 level of each pre-activation and where the f32 quantiser's result is
+    determined: farther than 8 * 2^-24 * (Q-1) levels from a threshold (expf within 2 ulp, the
+    add, the division and the multiplication within half an ulp each, times two)."""
+    t = quant_level_f64(pre, Q)
+    return t, half_margin(t) > 8 * 2.0 ** -24 * (Q - 1)
+
+
+def crafted_symbols(Q, code_shape, seed):
+    """Five symbol patches no encoder produced: two uniform random ones, all 0, all Q-1 (the SAME
+    padding around them must read 0.0, not lut[0]) and a checkerboard of 0 and Q-1."""
+    eh, ew, ec = code_shape
+    r = np.random.default_rng(np.random.PCG64(seed))
+    s = np.empty((5, eh, ew, ec), np.uint8)
+    s[:2] = r.integers(0, Q, (2, eh, ew, ec))
+    s[2] = 0
+    s[3] = Q - 1
+    yy, xx, cc = np.meshgrid(np.arange(eh), np.arange(ew), np.arange(ec), indexing="ij")
+    s[4] = np.where((yy + xx + cc) % 2 == 0, 0, Q - 1)
+    return s
+
+
+def decoder_reference(params, model_id, idx, Q):
+    """(ref_f, ref_u8, E32): the f64-accumulated oracle on these symbols, and per patch the max
+    distance of the same oracle accumulated in f32 from it — the reference's own f32 error."""
+    ref_f, ref_u8 = o.decoder(params, codec_mean(), codec_std(), idx, Q, model_id)
+    f32, _ = o.decoder(params, codec_mean(), codec_std(), idx, Q, model_id, acc=np.float32)
+    e32 = np.max(np.abs(f32.astype(np.float64) - ref_f), axis=(1, 2, 3))
+    return ref_f, ref_u8, e32
+
+
+def decoder_errors(codec, idx, ref, patches=None):
+    """check_codec's decoder half without its float bar: decode idx on the GPU, assert the byte
+    bar (within 1, and only where the oracle's float sits on a .5 rounding edge) and, given the
+    patches, the PSNR bar; returns the per-patch max |float - oracle|, the bytes and the floats."""
+    ref_f, ref_u8, _ = ref
+    rgb, f = codec.decode(idx, return_float=True)
+    assert f.shape == ref_f.shape and rgb.shape == ref_u8.shape
+    du = np.abs(rgb.astype(np.int16) - ref_u8.astype(np.int16))
+    assert int(du.max()) <= 1
+    edge = np.abs((ref_f - np.floor(ref_f)) - 0.5) < 1e-2
+    assert int(np.count_nonzero((du > 0) & ~edge)) == 0
+    if patches is not None:
+        p_gpu = o.dataset_psnr([(patches[i], rgb[i]) for i in range(len(patches))])
+        p_ref = o.dataset_psnr([(patches[i], ref_u8[i]) for i in range(len(patches))])
+        assert abs(p_gpu - p_ref) <= 0.02, (p_gpu, p_ref)
+    return np.max(np.abs(f.astype(np.float64) - ref_f), axis=(1, 2, 3)), rgb, f
+
+
+def float_bar(e32):
+    """The decoder's float bar where nothing is clipped: four times the reference's own f32 error
+    (the MFMA and Winograd summation orders differ from numpy's), never above DESIGN.md §4's 1e-2."""
+    return min(4.0 * float(e32), 1e-2)
+
+
+def wino4_float_bar(err_direct):
+    """F(4x4,3x3): the rule of test_gpu_wino4.py as it stands there, within twice the direct
+    form's error, that error floored at 1e-3 — and never above 1e-2.  The form's transforms
+    (constants up to 8) cost it a few times the error of the reference's own op order; on the
+    unclipped parameters it measures 1.1 to 4.1 E32 and up to 2.6 times the direct form's error,
+    both a few f32 ulp of the output, so the floor decides here."""
+    return min(2.0 * max(float(err_direct), 1e-3), 1e-2)
+
+
+def set_options(codec, **kw):
+    """Every structural option the parity tests vary, set explicitly (handles are shared)."""
+    opts = {"streams": 2, "fuse01": -1, "fuse_tail": -1, "s1_form": -1, "s2_form": -1, "chain": 0, "chain_wh": 2,
+            "chain_x": 0, "chain_j": 0}
+    assert set(kw) <= set(opts), kw
+    opts.update(kw)
+    for k, v in opts.items():
+        codec.set_option(k, v)
+
+
+def layer_index(codec, name):
+    return [lay[0] for lay in codec.layers()].index(name)
+
+
+def launched_kernel(codec, layer, n, codec_step=False):
+    """The kernel that runs `layer` for lane batch n: its own, or the fused launch it is inside
+    (tic_layer_kernel / tic_codec_kernel name layers inside a launch '').  Asks for the layers
+    up to `layer` only, so a forced tiling need not exist for the layers behind it."""
+    import ctypes as C
+    from tf_image_compression_amd._lib import check, lib
+    fn = lib().tic_codec_kernel if codec_step else lib().tic_layer_kernel
+    names = []
+    for i in range(layer + 1):
+        buf = C.create_string_buffer(160)
+        check(fn(codec._h, i, n, buf, 160), "tic_layer_kernel")
+        names.append(buf.value.decode())
+    while layer > 0 and names[layer] == "":
+        layer -= 1
+    return names[layer]
+
+
+def device_codec(codec, x):
+    """tic_codec_device on x (the only entry that runs the joined launch): (symbols, bytes)."""
+    eh, ew, ec = codec.code_shape
+    n = len(x)
+    nsym = n * eh * ew * ec
+    d_in, d_idx, d_rgb = codec.alloc(x.nbytes), codec.alloc(nsym), codec.alloc(x.nbytes)
+    try:
+        d_in.upload(x)
+        codec.memset_device(d_idx, 0xA5, nsym)  # nothing carried over from an earlier run
+        codec.memset_device(d_rgb, 0x5A, x.nbytes)
+        codec.codec_device(d_in, n, d_idx, d_rgb)
+        codec.synchronize()
+        return d_idx.download((n, eh, ew, ec), np.uint8), d_rgb.download(x.shape, np.uint8)
+    finally:
+        for b in (d_in, d_idx, d_rgb):
+            b.free()
+
+
 def codec_mean():
     from tf_image_compression_amd.weights import SYNTH_MEAN
     return SYNTH_MEAN

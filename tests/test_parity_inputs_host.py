@@ -1,0 +1,66 @@
+"""The input conditions the GPU tests of the quantiser, the dequantiser and the unclipped
+decoder rely on (test_gpu_quantiser.py, test_gpu_dequantiser.py), asserted on the CPU with the
+oracle alone: a later change of synthetic_params or structured_patches must not silently empty
+those tests.  Reference: the quantiser round(sigmoid(x) * (Q-1)) of model_0/model.py:136-138
+(tf.round: half to even), the dequantiser :148-155, denormalise + clip :250-259."""
+import numpy as np
+import pytest
+
+from conftest import structured_patches
+import gpu_checks as g
+from oracle import tic_oracle as o
+
+
+@pytest.mark.parametrize("cout", [64, 80])
+@pytest.mark.parametrize("Q", g.QUANT_QS)
+def test_quantiser_bias_vectors(Q, cout):
+    b, tie = g.quant_bias_vector(Q, cout)
+    assert b.dtype == np.float32 and b.shape == (cout,)
+    t = g.quant_level_f64(b, Q)
+    sym = g.quantize_f64(b, Q)
+    # every value but the tie itself sits more than 0.2 level from every rounding threshold, so
+    # the f32 sigmoid (a few 2^-24 (Q-1) levels of error, < 1e-4 level at Q = 256) cannot move it
+    assert np.all(g.half_margin(t[~tie]) > 0.2)
+    # the tie: +0 and -0, level (Q-1)/2 exactly, rounded half to even
+    assert np.count_nonzero(tie) >= 2 and np.any(np.signbit(b[tie])) and not np.all(np.signbit(b[tie]))
+    assert np.all(t[tie] == (Q - 1) / 2)
+    want = {2: 0, 3: 1, 4: 2, 6: 2, 16: 8, 255: 127, 256: 128}[Q]
+    assert np.all(sym[tie] == want)
+    # the clamp and the overflow values, both signs
+    for v in g.QUANT_EXTREMES:
+        assert np.all(sym[b == np.float32(v)] == Q - 1) and np.any(b == np.float32(v))
+        assert np.all(sym[b == np.float32(-v)] == 0) and np.any(b == np.float32(-v))
+    # the lowest and the highest threshold from both sides, and every level in between for small Q
+    assert {0, 1, Q - 2, Q - 1} <= set(sym.tolist())
+    if Q <= 16:
+        assert set(sym.tolist()) == set(range(Q))
+    # neighbouring channels differ wherever the symbols allow it, and no packed u32 (four
+    # consecutive channels) holds one symbol only
+    same = np.count_nonzero(sym[1:] == sym[:-1])
+    assert same == 0 if Q >= 3 else same <= cout // 8
+    groups = [len(set(sym[i:i + 4].tolist())) for i in range(0, cout, 4)]
+    assert min(groups) >= 2 and (Q < 16 or min(groups) >= 3)
+
+
+GAIN_CASES = [(0, 4.0), (3, 1.0)]  # (model, gain of the last encoder layer)
+
+
+@pytest.mark.parametrize("model_id,gain", GAIN_CASES)
+def test_all_256_levels_reached(model_id, gain):
+    P, Q = 64, 256
+    params = g.gained_params(model_id, gain)
+    pre, idx = o.encoder(params, g.codec_mean(), g.codec_std(), structured_patches(4, P, seed=5), P, Q, model_id)
+    assert set(idx.ravel().tolist()) == set(range(256))
+    assert float(np.abs(pre).max()) > 16  # the saturated ends are reached with room
+    _, safe = g.quant_rule_excluded(pre, Q)
+    assert float(np.mean(~safe)) <= 1e-3
+
+
+@pytest.mark.parametrize("model_id,P", g.UNCLIPPED_CASES)
+def test_unclipped_params_leave_nothing_clipped(model_id, P):
+    params = g.unclipped_params(model_id)
+    x = structured_patches(3, P, seed=61 + model_id)
+    _, idx = o.encoder(params, g.codec_mean(), g.codec_std(), x, P, 2, model_id)
+    ref_f, _ = o.decoder(params, g.codec_mean(), g.codec_std(), idx, 2, model_id)
+    share, span = g.clipped_share_and_span(ref_f)
+    assert share <= 0.01 and span >= 100, (share, span)
