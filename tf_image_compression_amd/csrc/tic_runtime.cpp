@@ -40,6 +40,15 @@ int fail(int code, const char* fmt, ...) {
   return code;
 }
 
+std::string strf(const char* fmt, ...) {
+  char buf[160];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof(buf), fmt, ap);
+  va_end(ap);
+  return buf;
+}
+
 #define HIP_TRY(expr)                                                                       \
   do {                                                                                      \
     hipError_t e_ = (expr);                                                                 \
@@ -196,12 +205,27 @@ int form_fallback(int form, int pass) {
   return form == 2 ? 0 : -1;
 }
 
-const tic::ConvEntry* find_conv(int mode, int cin, int cout, int act, int res, int in, int outm, int hg = 0,
-                                int wg = 0, int n = 0, int form = 0) {
+// A conv layer's kernel signature: the registry fields a compiled instance must match, and the
+// rows of the grid its tilings are ranked by (hg: output rows; a transposed layer's input rows).
+struct ConvSig {
+  int mode, cin, cout, act, res, in, out, hg;
+  bool matches(const tic::ConvEntry& c) const {
+    return c.cin == cin && c.cout == cout && c.act == act && c.res == res && c.in == in && c.out == out;
+  }
+};
+
+const tic::ConvEntry* conv_registry(int mode, int* cnt) {
   const tic::ConvEntry* (*regs[3])(int*) = {tic::conv_registry_s1, tic::conv_registry_s2,
                                            tic::conv_registry_t2};
+  return regs[mode](cnt);
+}
+
+// (wg: the grid's columns where it is not square, tic_conv3x3_device)
+const tic::ConvEntry* find_conv(const ConvSig& s, int n, int form, int wg = -1) {
+  const int hg = s.hg;
+  if (wg < 0) wg = hg;
   int cnt = 0;
-  const tic::ConvEntry* e = regs[mode](&cnt);
+  const tic::ConvEntry* e = conv_registry(s.mode, &cnt);
   int fth = 0, fns = 0, fwl = -1, fwr = 0;
   if (const char* f = getenv("TIC_FORCE_TILE")) sscanf(f, "%d,%d,%d,%d", &fth, &fns, &fwl, &fwr);
   if (!fth) fwl = -1;
@@ -213,7 +237,7 @@ const tic::ConvEntry* find_conv(int mode, int cin, int cout, int act, int res, i
     bool best_ok = false;
     for (int i = 0; i < cnt; ++i) {
       const tic::ConvEntry& c = e[i];
-      if (c.cin != cin || c.cout != cout || c.act != act || c.res != res || c.in != in || c.out != outm) continue;
+      if (!s.matches(c)) continue;
       if (fth && (c.th != fth || c.nsplit != fns || (fwr > 0 && c.wr != fwr))) continue;
       if (!form_match(c, fm, fwl)) continue;
       // patches too large for F(4x4,3x3)'s 32-bit offsets run the next form (the codec's
@@ -243,20 +267,15 @@ const tic::ConvEntry* find_conv(int mode, int cin, int cout, int act, int res, i
 }
 
 // Every compiled tiling of this layer signature within one form (all bit-identical).
-std::vector<const tic::ConvEntry*> conv_candidates(int mode, int cin, int cout, int act, int res, int in, int outm,
-                                                   int form, int hg, int wg) {
-  const tic::ConvEntry* (*regs[3])(int*) = {tic::conv_registry_s1, tic::conv_registry_s2,
-                                           tic::conv_registry_t2};
+std::vector<const tic::ConvEntry*> conv_candidates(const ConvSig& s, int form) {
   int cnt = 0;
-  const tic::ConvEntry* e = regs[mode](&cnt);
+  const tic::ConvEntry* e = conv_registry(s.mode, &cnt);
   std::vector<const tic::ConvEntry*> out;
   for (int pass = 0; pass < 3 && out.empty(); ++pass) {
     const int fm = form_fallback(form, pass);
     if (fm < 0) break;
     for (int i = 0; i < cnt; ++i)
-      if (e[i].cin == cin && e[i].cout == cout && e[i].act == act && e[i].res == res && e[i].in == in &&
-          e[i].out == outm && entry_form(e[i]) == fm && wino4_fits(e[i], hg, wg))
-        out.push_back(&e[i]);
+      if (s.matches(e[i]) && entry_form(e[i]) == fm && wino4_fits(e[i], s.hg, s.hg)) out.push_back(&e[i]);
   }
   return out;
 }
@@ -688,8 +707,9 @@ static float median_of(std::vector<float> v) {
   return v.empty() ? 1e30f : v[v.size() / 2];
 }
 
+// (words(v): how the log names variant v, where "variant v" says too little)
 int time_variants(hipStream_t st, int nvar, int reps, const std::function<bool(int)>& launch, int* best,
-                  const char* label = "", int n = 0) {
+                  const char* label = "", int n = 0, const std::function<std::string(int)>& words = nullptr) {
   static const bool log = getenv("TIC_TUNE_LOG") != nullptr;
   Event t0, t1;
   HIP_TRY(t0.create());
@@ -704,7 +724,9 @@ int time_variants(hipStream_t st, int nvar, int reps, const std::function<bool(i
       HIP_TRY(hipEventSynchronize(t1.e));
       float ms = 0.f;
       HIP_TRY(hipEventElapsedTime(&ms, t0.e, t1.e));
-      if (log) fprintf(stderr, "tune %-22s n=%d variant %d : %.2f us\n", label, n, v, 1e3f * ms / reps);
+      if (log)
+        fprintf(stderr, "tune %-22s n=%d %s : %.2f us\n", label, n,
+                (words ? words(v) : "variant " + std::to_string(v)).c_str(), 1e3f * ms / reps);
       samples[v].push_back(ms);
     }
   }
@@ -781,12 +803,50 @@ RgbOutForm rgb_out_form() {
   if (s == "scatter") return {3, 6};
   return {6, 12};
 }
-int rgb_out_variant(const std::map<int, int>& tuned, int n) {
+
+// ---- Kernel selection: one function per launch kind, read by the run path, the tuners and the
+// introspection entries alike ----
+ConvSig conv_sig(const tic_handle* h, int i) {
+  const LayerRT& l = h->layers[i];
+  const LayerDef& d = l.def;
+  const bool last_enc = !h->rmbe() && i == h->n_enc - 1, first_dec = !h->rmbe() && i == h->n_enc;
+  return {d.kind, d.cin, d.cout, d.act, d.residual, first_dec ? tic::IN_IDX : tic::IN_F32,
+          last_enc ? tic::OUT_QUANT : tic::OUT_F32, d.kind == K_T2 ? l.h_in : l.h_out};
+}
+// a plain conv layer's instance for lane batch n: the tuned entry if it can run the patch, else
+// find_conv's pick (nullptr: nothing compiled for the signature)
+const tic::ConvEntry* pick_conv(const tic_handle* h, int i, int n) {
+  const LayerRT& l = h->layers[i];
+  const ConvSig s = conv_sig(h, i);
+  auto it = l.tuned.find(tkey(h, l, n));
+  if (it != l.tuned.end() && wino4_fits(*it->second, s.hg, s.hg)) return it->second;
+  return find_conv(s, n, layer_form(h, l));
+}
+// fused-pair variants: enc01_kernel's keyed by -n on layer 0, dec10_kernel's by n on layer L-2
+int enc01_variant(const tic_handle* h, int n) {
+  if (const char* t = getenv("TIC_ENC01_VARIANT")) return atoi(t);
+  const std::map<int, int>& tuned = h->layers[0].tuned_var;
+  auto it = tuned.find(-n);
+  return it != tuned.end() ? it->second : tic::kEnc01Default;
+}
+int dec10_variant(const tic_handle* h, int n) {
+  if (const char* t = getenv("TIC_DEC10_VARIANT")) return atoi(t);
+  const std::map<int, int>& tuned = h->layers[h->layers.size() - 2].tuned_var;
+  auto it = tuned.find(n);
+  return it != tuned.end() ? it->second : tic::kDec10Default;
+}
+int rgb_in_variant(const tic_handle* h, int n) {
+  const std::map<int, int>& tuned = h->layers[0].tuned_var;
+  auto it = tuned.find(n);
+  return it != tuned.end() ? it->second : kRgbInDefault;
+}
+int rgb_out_variant(const tic_handle* h, int n) {
   const RgbOutForm fm = rgb_out_form();
   if (const char* t = getenv("TIC_RGB_OUT_TILE")) {  // tests: force tiling t of the form
     const int v = fm.lo + atoi(t);
     if (fm.has(v)) return v;
   }
+  const std::map<int, int>& tuned = h->layers.back().tuned_var;
   auto it = tuned.find(n);
   return it != tuned.end() && fm.has(it->second) ? it->second : fm.lo;
 }
@@ -795,23 +855,27 @@ struct Prof {
   hipEvent_t* ev;  // 2 per layer, or nullptr
 };
 
-// encode_0 -> encode_1 through one enc01_kernel launch (opt-in "fuse01")
-static bool fuses01(const tic_handle* h) {
-  if (!h->fuse01 || h->layers.size() <= 2) return false;
+// Whether the topology has the fused pairs' layers at all, whatever the flags say (pwino_layer
+// reads these, so a layer's form never depends on a tuned flag): encode_0 -> encode_1 in one of
+// enc01_kernel's widths; the decoder's last two layers in one of dec10_kernel's, with the VALU
+// last-layer form, whose summation order the fused kernel reproduces.
+static bool enc01_shape(const tic_handle* h) {
+  if (h->layers.size() <= 2) return false;
   const LayerDef& d = h->layers[1].def;
   const bool ok = (d.cin == 32 && d.cout == 32) || (d.cin == 16 && d.cout == 32) || (d.cin == 32 && d.cout == 64);
   return ok && d.kind == K_S2 && d.act == 1 && !d.residual && !(!h->rmbe() && h->n_enc == 2);
 }
-
-// decoder's last two layers through one dec10_kernel launch (option "fuse_tail"; only with
-// the VALU last-layer form, whose summation order the fused kernel reproduces)
-static bool fuses_tail(const tic_handle* h) {
+static bool dec10_shape(const tic_handle* h) {
   const int L = (int)h->layers.size();
-  if (!h->fuse_tail || L < 3 || rgb_out_form().lo != 6) return false;
+  if (L < 3 || rgb_out_form().lo != 6) return false;
   const LayerDef& d = h->layers[L - 2].def;
   const bool ok = (d.cin == 32 && d.cout == 32) || (d.cin == 32 && d.cout == 16) || (d.cin == 64 && d.cout == 32);
   return ok && d.kind == K_T2 && d.act == 1 && !d.residual && !(!h->rmbe() && L - 2 == h->n_enc);
 }
+// encode_0 -> encode_1 through one enc01_kernel launch (option "fuse01")
+static bool fuses01(const tic_handle* h) { return h->fuse01 && enc01_shape(h); }
+// decoder's last two layers through one dec10_kernel launch (option "fuse_tail")
+static bool fuses_tail(const tic_handle* h) { return h->fuse_tail && dec10_shape(h); }
 
 // Chains: layers [li, chain_end) run in one launch when the handle's "chain" option is on,
 // li starts a run of >= 2 stride-1 64->64 layers inside one network half (the encoder's last
@@ -920,31 +984,6 @@ static ChainSpan chain_span_at(const tic_handle* h, int li) {
   }
   return sp;
 }
-// every chain launch of the network, in order (as run_layers walks it)
-static std::vector<ChainSpan> chain_spans(const tic_handle* h) {
-  std::vector<ChainSpan> v;
-  const int L = (int)h->layers.size();
-  for (int i = 1; i < L - 1; ++i) {
-    const ChainSpan sp = chain_span_at(h, i);
-    if (!sp.valid()) continue;
-    v.push_back(sp);
-    i = sp.last();
-  }
-  return v;
-}
-// layer i runs inside some wino_chain_kernel launch
-static bool in_chain(const tic_handle* h, int i) {
-  for (const ChainSpan& sp : chain_spans(h))
-    if (sp.start <= i && i <= sp.last()) return true;
-  return false;
-}
-static bool any_chain(const tic_handle* h) { return !chain_spans(h).empty(); }
-// whether the option "chain_x" changes the launch plan at all (level 2: a decode_2 behind a tail)
-static bool any_chain_x(const tic_handle* h, int level = 1) {
-  for (const ChainSpan& sp : chain_spans(h))
-    if (level >= 2 ? sp.tail2 : (sp.head || sp.tail)) return true;
-  return false;
-}
 
 // The codec step's joined launch (option "chain_j", wino_chain.h CH_JOIN): the chain launch that
 // starts at layer li is the encoder's last one (head, run, quantiser) and the decoder's first
@@ -967,12 +1006,128 @@ static bool chain_join_at(const tic_handle* h, int li, ChainSpan* dec) {
   *dec = d;
   return true;
 }
-// the layer at which tic_codec_device's joined launch starts, or -1 when it runs two launches
-static int codec_join_start(const tic_handle* h) {
-  ChainSpan d;
-  for (const ChainSpan& sp : chain_spans(h))
-    if (sp.end == h->n_enc && chain_join_at(h, sp.start, &d)) return sp.start;
-  return -1;
+
+// ---- Launch plan: which launches run layers [l0, l1), the single source the run path
+// (run_layers), the step tuner and the introspection entries read ----
+enum LaunchKind { LK_ENC01, LK_DEC10, LK_CHAIN, LK_FIRST, LK_LAST, LK_CONV };
+struct Launch {
+  LaunchKind kind = LK_CONV;
+  int first = 0, last = 0;  // the layers it covers, inclusive
+  // chain launches: the encoder-side span (or the only one), the decoder-side span joined to it,
+  // and wino_chain.h's HT template bits
+  ChainSpan sp, jd;
+  bool join = false;
+  int ht = 0;
+  const ChainSpan& tail_span() const { return join ? jd : sp; }  // the span that carries the tail
+};
+// Precedence at each layer: the fused first pair, the fused decoder tail, a chain launch (joined
+// to the decoder-side one where allow_join and chain_join_at say so), else the layer alone.  A
+// fused launch is planned only where all its layers lie inside [l0, l1).  allow_join: not while
+// per-layer events are recorded or the handle is inside per-layer tuning.  No HIP calls.
+static std::vector<Launch> plan_launches(const tic_handle* h, int l0, int l1, bool allow_join) {
+  const int L = (int)h->layers.size();
+  std::vector<Launch> plan;
+  for (int li = l0; li < l1; ++li) {
+    Launch p;
+    p.first = p.last = li;
+    p.kind = li == 0 ? LK_FIRST : (li == L - 1 ? LK_LAST : LK_CONV);
+    if (li == 0 && li + 1 < l1 && fuses01(h)) {
+      p.kind = LK_ENC01;
+      p.last = 1;
+    } else if (li == L - 2 && li + 1 < l1 && fuses_tail(h)) {
+      p.kind = LK_DEC10;
+      p.last = L - 1;
+    } else if ((p.sp = chain_span_at(h, li)).valid()) {
+      p.join = allow_join && chain_join_at(h, li, &p.jd) && p.jd.last() < l1;
+      if (p.sp.last() < l1) {
+        const ChainSpan& t = p.tail_span();
+        const bool tail2_pw = t.tail2 && layer_form(h, h->layers[t.end + 1]) == 1;
+        p.kind = LK_CHAIN;
+        p.last = t.last();
+        p.ht = (p.sp.head ? tic::CH_HEAD : 0) | (t.tail ? tic::CH_TAIL : 0) | (t.tail2 ? tic::CH_TAIL2 : 0) |
+               (tail2_pw ? tic::CH_TAIL2_PW : 0) | (p.join ? tic::CH_JOIN : 0);
+      }
+    }
+    plan.push_back(p);
+    li = p.last;
+  }
+  return plan;
+}
+// queries on the plan of a whole step (tic_codec_device's pass over both halves, the rmbe net's)
+template <class F>
+static bool plan_any(const tic_handle* h, F pred) {
+  for (const Launch& p : plan_launches(h, 0, (int)h->layers.size(), true))
+    if (pred(p)) return true;
+  return false;
+}
+static bool any_chain(const tic_handle* h) {
+  return plan_any(h, [](const Launch& p) { return p.kind == LK_CHAIN; });
+}
+// whether the option "chain_x" changes the launch plan at all (level 2: a decode_2 behind a tail)
+static bool any_chain_x(const tic_handle* h, int level = 1) {
+  const int bits = level >= 2 ? tic::CH_TAIL2 : tic::CH_HEAD | tic::CH_TAIL;
+  return plan_any(h, [&](const Launch& p) { return (p.ht & bits) != 0; });
+}
+// whether tic_codec_device's pass runs the joined launch (it runs two passes otherwise)
+static bool plan_joined(const tic_handle* h) {
+  return plan_any(h, [](const Launch& p) { return p.join; });
+}
+
+// The kernel instance a launch runs for lane batch n.
+static int launch_name(const tic_handle* h, const Launch& p, int n, char* buf, size_t cap) {
+  const LayerDef& d = h->layers[p.first].def;
+  const char* tf[2] = {"false", "true"};
+  static const int th[3] = {4, 8, 16}, tw[3] = {64, 32, 16};
+  switch (p.kind) {
+    case LK_CHAIN: {
+      const bool first_dec = !h->rmbe() && p.sp.s1 == h->n_enc, last_enc = !h->rmbe() && p.sp.end - 1 == h->n_enc - 1;
+      snprintf(buf, cap, "wino_chain_kernel<%d,%d,%d,%d>", first_dec ? 1 : 0, last_enc ? 1 : 0, h->chain_wh, p.ht);
+      break;
+    }
+    case LK_DEC10: {
+      const int v = dec10_variant(h, n);
+      snprintf(buf, cap, "dec10_kernel<%d,%d,false,%d,0,%d,%s,%s>", d.cin, d.cout, (v & 2) ? 5 : 2, (v & 4) ? 8 : 4,
+               tf[(v >> 3) & 1], tf[!(v & 1)]);
+      break;
+    }
+    case LK_ENC01: {
+      const int v = enc01_variant(h, n);
+      static const int th1[5] = {2, 4, 2, 4, 8};
+      snprintf(buf, cap, "enc01_kernel<%d,%d,%d,%s,%s,%s>", d.cout, h->layers[1].def.cout, th1[v % 5], tf[!h->rmbe()],
+               tf[v >= 2], tf[getenv("TIC_ENC01_TIMING") != nullptr]);
+      break;
+    }
+    case LK_FIRST:
+      snprintf(buf, cap, "conv_rgb_s2_kernel<%d,%d,%s>", d.cout, th[rgb_in_variant(h, n) % 3], tf[!h->rmbe()]);
+      break;
+    case LK_LAST: {
+      const int v = rgb_out_variant(h, n);
+      if (v >= 6)
+        snprintf(buf, cap, "%s<%d,%d>", v >= 9 ? "convT_rgb_valu_persist_kernel" : "convT_rgb_valu_kernel", d.cin,
+                 tw[v % 3]);
+      else
+        snprintf(buf, cap, "%s<%d,%d>", v >= 3 ? "convT_rgb_scatter_kernel" : "convT_rgb_kernel", d.cin, th[v % 3]);
+      break;
+    }
+    case LK_CONV: {
+      const tic::ConvEntry* e = pick_conv(h, p.first, n);
+      if (!e) return fail(TIC_EUNSUPPORTED, "layer %d has no compiled kernel", p.first);
+      if (e->wlds == 6)
+        snprintf(buf, cap, "conv3x3_pwino_kernel<%d,%d,%d,%d,%d,%s,%d,%d>", e->mode, e->cin, e->cout, e->wr, e->act,
+                 tf[e->res != 0], e->in, e->out);
+      else if (e->wlds == 5)
+        snprintf(buf, cap, "conv3x3_wino4_kernel<%d,%d,%d,%d,%s,%d,%d>", e->cin, e->cout, e->th / 4, e->act,
+                 tf[e->res != 0], e->in, e->out);
+      else if (e->wlds == 4)
+        snprintf(buf, cap, "conv3x3_wino_kernel<%d,%d,%d,%d,%d,%d,%s,%d,%d>", e->cin, e->cout, e->th / 2, e->wr,
+                 e->nsplit, e->act, tf[e->res != 0], e->in, e->out);
+      else
+        snprintf(buf, cap, "conv3x3<%d,%d,%d,%d,%d,%d,%d,%d,%s,%d,%d>", e->mode, e->cin, e->cout, e->th, e->wr,
+                 e->nsplit, e->wlds, e->act, tf[e->res != 0], e->in, e->out);
+      break;
+    }
+  }
+  return TIC_OK;
 }
 
 // Whether stride-2 / transposed layer i may run the polyphase Winograd form (s2_form 1): only
@@ -994,13 +1149,8 @@ bool pwino_layer(const tic_handle* h, int i) {
   // (profiles/ab_r06_pwino_il.json); those layers keep the direct form
   if (d.cout % 64 != 0 && d.cout != 32) return false;
   if (d.cin % 16 != 0 || d.cin == 80) return false;
-  const bool relu = d.act == 1 && !d.residual;
-  if (i == 1 && d.kind == K_S2 && relu && !(!h->rmbe() && h->n_enc == 2) &&
-      ((d.cin == 32 && d.cout == 32) || (d.cin == 16 && d.cout == 32) || (d.cin == 32 && d.cout == 64)))
-    return false;  // enc01's encode_1
-  if (i == L - 2 && d.kind == K_T2 && relu && rgb_out_form().lo == 6 && !(!h->rmbe() && L - 2 == h->n_enc) &&
-      ((d.cin == 32 && d.cout == 32) || (d.cin == 32 && d.cout == 16) || (d.cin == 64 && d.cout == 32)))
-    return false;  // dec10's decode_1
+  if (i == 1 && enc01_shape(h)) return false;      // enc01's encode_1
+  if (i == L - 2 && dec10_shape(h)) return false;  // dec10's decode_1
   if (h->s1_form == 1) {
     auto s1_64 = [&](int j) {
       return j > 0 && j < L - 1 && h->layers[j].def.kind == K_S1 && h->layers[j].def.cin == 64 &&
@@ -1012,25 +1162,290 @@ bool pwino_layer(const tic_handle* h, int i) {
   return true;
 }
 
-// Run layers [l0, l1) for n patches. Input: `in` (u8 patches, f32 windows or u8 symbols);
-// outputs per-position flags.  Buffers rotate through h->ws.  A pass over both halves of a
-// codec ([0, L): tic_codec_device) reads the decoder's symbols from d_idx, and runs the
-// encoder's last and the decoder's first chain launch as one where chain_join_at plans it.
 static constexpr int kMarkCap = 1024;  // event pairs per lane
 
+// One run_layers pass: its lane, batch and buffers (`in`: u8 patches, f32 windows or u8 symbols;
+// sym_in: the decoder's input, the symbols this same pass wrote or the caller's).
+struct Pass {
+  tic_handle* h;
+  Lane& ln;
+  const void *in, *sym_in;
+  int n;
+  uint8_t* d_idx;
+  float* d_pre;
+  uint8_t* d_rgb;
+  float* d_f32;
+  // timing probe only (results invalid): TIC_PROBE_SKIP = bit mask of plain-conv layers
+  // whose launch is left out, to price a group of layers inside the whole step
+  unsigned long long probe_skip;
+};
+// The workspace rotation of a pass: buffers rotate through ln.ws.
+struct Rot {
+  int cur = -1;       // ws index holding the current activation (-1: external input)
+  int block_in = -1;  // ws index of the enclosing res_block's input
+  int dst = -1;       // ws index the launch being enqueued writes
+};
+static const float* rot_src(const Pass& ps, const Rot& r) { return r.cur >= 0 ? ps.ln.ws[r.cur] : nullptr; }
+static void set_norm(const tic_handle* h, float* mean, float* std) {
+  for (int c = 0; c < 3; ++c) {
+    mean[c] = h->mean[c];
+    std[c] = h->std[c];
+  }
+}
+
+static int enqueue_enc01(const Pass& ps, const Rot& r) {
+  tic_handle* h = ps.h;
+  hipStream_t const st = ps.ln.stream;
+  const int n = ps.n;
+  LayerRT &lay = h->layers[0], &l1r = h->layers[1];
+  const LayerDef& d = lay.def;
+  tic::Enc01Args a{};
+  a.in = ps.in;
+  a.wp0 = lay.d_w;
+  a.b0 = lay.d_b;
+  a.wp1 = l1r.d_w;
+  a.b1 = l1r.d_b;
+  a.out = ps.ln.ws[r.dst];
+  a.H = a.W = lay.h_in;
+  a.H1 = a.W1 = lay.h_out;
+  a.H2 = a.W2 = l1r.h_out;
+  a.pad0y = a.pad0x = same_pad(d.kind, lay.h_in);
+  a.pad1y = a.pad1x = same_pad(K_S2, l1r.h_in);
+  a.nlut = h->d_nlut;
+  set_norm(h, a.mean, a.std);
+  if (getenv("TIC_ENC01_TIMING")) {  // phase timestamps (tools/chain_timing.py --enc01)
+    // sized for the largest grid of any variant (2-row tiles)
+    int rc2 = probe_stamps(ps.ln, 2, n * ((l1r.h_out + 1) / 2) * ((l1r.h_out + 15) / 16), st, &a.tstamp);
+    if (rc2) return rc2;
+  }
+  auto launch = [&](int v) { return tic::launch_enc01(d.cout, l1r.def.cout, !h->rmbe(), a, n, st, v); };
+  int var = enc01_variant(h, n);
+  if (h->tune_reps > 0 && !getenv("TIC_ENC01_VARIANT") && !lay.tuned_var.count(-n)) {
+    if (int rc = time_variants(st, tic::enc01_variants(), h->tune_reps, launch, &var, "enc01", n)) return rc;
+    lay.tuned_var[-n] = var;
+  }
+  if (!launch(var))
+    return fail(TIC_EUNSUPPORTED, "fused first layers %d->%d->%d not compiled", d.cin, d.cout, l1r.def.cout);
+  return TIC_OK;
+}
+
+static int enqueue_dec10(const Pass& ps, const Rot& r) {
+  tic_handle* h = ps.h;
+  hipStream_t const st = ps.ln.stream;
+  const int n = ps.n, L = (int)h->layers.size();
+  LayerRT &lay = h->layers[L - 2], &last_l = h->layers[L - 1];
+  const LayerDef& d = lay.def;
+  tic::Dec10Args a{};
+  a.in = rot_src(ps, r);
+  a.wp1 = lay.d_w;
+  a.w1raw = lay.d_w3;
+  a.b1 = lay.d_b;
+  a.H = a.W = lay.h_in;
+  a.rgb.wraw = last_l.d_w3;
+  a.rgb.bias = last_l.d_b;
+  a.rgb.out_u8 = ps.d_rgb;
+  a.rgb.out_f32 = ps.d_f32;
+  a.rgb.H = a.rgb.W = last_l.h_in;
+  a.rgb.num_cus = h->num_cus;
+  a.rgb.grid_cap = h->persist_grid;
+  set_norm(h, a.rgb.mean, a.rgb.std);
+  auto launch = [&](int v) { return tic::launch_dec10(d.cin, d.cout, a, n, st, v); };
+  int var = dec10_variant(h, n);
+  if (h->tune_reps > 0 && !getenv("TIC_DEC10_VARIANT") && !lay.tuned_var.count(n)) {
+    if (int rc = time_variants(st, tic::dec10_variants(), h->tune_reps, launch, &var, "dec10", n)) return rc;
+    lay.tuned_var[n] = var;
+  }
+  if (!launch(var))
+    return fail(TIC_EUNSUPPORTED, "fused decoder tail %d->%d->3 not compiled", d.cin, d.cout);
+  return TIC_OK;
+}
+
+static int enqueue_chain(const Pass& ps, const Rot& r, const Launch& p) {
+  tic_handle* h = ps.h;
+  Lane& ln = ps.ln;
+  hipStream_t const st = ln.stream;
+  const int n = ps.n;
+  const ChainSpan &sp = p.sp, &tsp = p.tail_span();
+  const int s1 = sp.s1, ce = sp.end, nl = ce - s1 + (p.join ? p.jd.end - p.jd.s1 : 0);
+  const int te = tsp.end;             // the tail's layer
+  const LayerRT& lr = h->layers[s1];  // the run's first stride-1 layer
+  const bool first_dec_c = !h->rmbe() && s1 == h->n_enc;
+  const bool last_enc_c = !h->rmbe() && ce - 1 == h->n_enc - 1;
+  const int R = ((lr.h_in + 7) / 8) * ((lr.h_in + 7) / 8);  // 8x8 regions per patch
+  const float* src = rot_src(ps, r);
+  float* const dst = ln.ws[r.dst];
+  // hand-offs + 1 (joined: the junction is one more slot of the same protocol)
+  int rc = ensure_chain(h, ln, nl + (sp.head ? 1 : 0) + (tsp.tail ? 1 : 0), n, R);
+  if (rc) return rc;
+  tic::ChainArgs a{};
+  for (int k = 0; k < nl; ++k) {  // (joined: the decoder's run follows the encoder's, s1 + k)
+    const LayerRT& lk = h->layers[s1 + k];
+    a.layer[k] = {lk.d_ww, lk.d_b, lk.def.act, lk.def.residual};
+  }
+  a.nl = nl;
+  a.nq = p.join ? ce - s1 - 1 : -1;
+  a.in = first_dec_c ? ps.sym_in : (const void*)src;
+  a.lut = h->d_lut;
+  a.out = last_enc_c ? ps.d_pre : dst;
+  a.qout = last_enc_c ? ps.d_idx : nullptr;
+  a.qscale = (float)(h->Q - 1);
+  a.H = a.W = lr.h_in;
+  a.rh = a.rw = (lr.h_in + 7) / 8;
+  a.n = n;
+  a.xbuf = ln.xbuf;
+  a.flags = ln.cflags;
+  a.ctl = ln.ctl;
+  a.dispatch_order = chain_launch_order(h, n, R);
+  if (sp.head) {  // the stride-2 layer in front (the launch's first): its direct packing, input = src
+    const LayerRT& hl = h->layers[p.first];
+    a.head = {hl.d_w, hl.d_b, hl.def.act, 0};
+    a.head_in = src;
+    a.hH = a.hW = hl.h_in;
+    a.hpad = same_pad(K_S2, hl.h_in);
+  }
+  if (tsp.tail) {  // the transposed layer behind (layer te), writing the next activation
+    const LayerRT& tl = h->layers[te];
+    a.tail = {tl.d_w, tl.d_b, tl.def.act, 0};
+    a.tail_out = dst;
+  }
+  if (tsp.tail2) {  // and the next one (decode_2), whose output is the next activation instead;
+                    // in its polyphase Winograd form where the s2_form policy runs it so
+    const LayerRT& tl2 = h->layers[te + 1];
+    a.tail2 = {(p.ht & tic::CH_TAIL2_PW) ? tl2.d_wp : tl2.d_w, tl2.d_b, tl2.def.act, 0};
+    a.tail2_out = dst;
+  }
+  if (const char* pr = getenv("TIC_CHAIN_PROBE")) a.probe = atoi(pr);
+  if (getenv("TIC_CHAIN_TIMING")) {  // phase timestamps of this launch (tools/chain_timing.py)
+    int rc2 = probe_stamps(ln, first_dec_c || tsp.tail ? 1 : 0, n * R, st, &a.tstamp);
+    if (rc2) return rc2;
+  }
+  const int inm = first_dec_c ? tic::IN_IDX : tic::IN_F32, outm = last_enc_c ? tic::OUT_QUANT : tic::OUT_F32;
+  if (!tic::launch_wino_chain(inm, outm, a, st, h->chain_wh, p.ht))
+    return fail(TIC_EUNSUPPORTED, "no chain kernel for layers %d..%d", p.first, p.last);
+  return TIC_OK;
+}
+
+static int enqueue_first(const Pass& ps, const Rot& r) {
+  tic_handle* h = ps.h;
+  hipStream_t const st = ps.ln.stream;
+  const int n = ps.n;
+  LayerRT& lay = h->layers[0];
+  const LayerDef& d = lay.def;
+  tic::RgbInArgs a{};
+  a.in = ps.in;
+  a.wp = lay.d_w;
+  a.bias = lay.d_b;
+  a.out = ps.ln.ws[r.dst];
+  a.H = a.W = lay.h_in;
+  a.Ho = a.Wo = lay.h_out;
+  a.pad_y = a.pad_x = same_pad(d.kind, lay.h_in);
+  set_norm(h, a.mean, a.std);
+  auto launch = [&](int v) { return tic::launch_rgb_in(d.cout, !h->rmbe(), a, n, st, v); };
+  int var = rgb_in_variant(h, n);
+  if (h->tune_reps > 0 && !lay.tuned_var.count(n)) {
+    if (int rc = time_variants(st, tic::rgb_in_variants(), h->tune_reps, launch, &var, "rgb_in", n)) return rc;
+    lay.tuned_var[n] = var;
+  }
+  if (!launch(var))
+    return fail(TIC_EUNSUPPORTED, "first layer %s: width %d not compiled", d.name.c_str(), d.cout);
+  return TIC_OK;
+}
+
+static int enqueue_last(const Pass& ps, const Rot& r) {
+  tic_handle* h = ps.h;
+  hipStream_t const st = ps.ln.stream;
+  const int n = ps.n;
+  LayerRT& lay = h->layers.back();
+  const LayerDef& d = lay.def;
+  tic::RgbOutArgs a{};
+  a.in = rot_src(ps, r);
+  a.wp = lay.d_w;
+  a.wp2 = lay.d_w2;
+  a.wraw = lay.d_w3;
+  a.num_cus = h->num_cus;
+  a.grid_cap = h->persist_grid;
+  a.bias = lay.d_b;
+  a.out_u8 = ps.d_rgb;
+  a.out_f32 = ps.d_f32;
+  a.H = a.W = lay.h_in;
+  set_norm(h, a.mean, a.std);
+  auto launch = [&](int v) { return tic::launch_rgb_out(d.cin, a, n, st, v); };
+  const RgbOutForm fm = rgb_out_form();
+  auto it = lay.tuned_var.find(n);
+  int var = rgb_out_variant(h, n);
+  if (h->tune_reps > 0 && (it == lay.tuned_var.end() || !fm.has(it->second)) && !getenv("TIC_RGB_OUT_TILE")) {
+    auto tile = [&](int v) { return launch(fm.lo + v); };
+    if (int rc = time_variants(st, fm.hi - fm.lo, h->tune_reps, tile, &var, "rgb_out", n)) return rc;
+    var += fm.lo;
+    lay.tuned_var[n] = var;
+  }
+  if (!launch(var))
+    return fail(TIC_EUNSUPPORTED, "last layer %s: width %d not compiled", d.name.c_str(), d.cin);
+  return TIC_OK;
+}
+
+static int enqueue_conv(const Pass& ps, const Rot& r, int li) {
+  tic_handle* h = ps.h;
+  hipStream_t const st = ps.ln.stream;
+  const int n = ps.n;
+  LayerRT& lay = h->layers[li];
+  const LayerDef& d = lay.def;
+  const ConvSig s = conv_sig(h, li);
+  const bool first_dec = s.in == tic::IN_IDX, last_enc = s.out == tic::OUT_QUANT;
+  const tic::ConvEntry* e = pick_conv(h, li, n);
+  if (!e)
+    return fail(TIC_EUNSUPPORTED, "no kernel for layer %s (kind %d %d->%d act %d res %d in %d out %d)", d.name.c_str(),
+                d.kind, d.cin, d.cout, d.act, d.residual, s.in, s.out);
+  tic::ConvArgs a{};
+  a.in = first_dec ? ps.sym_in : (const void*)rot_src(ps, r);
+  a.wp = lay.d_w;
+  a.bias = lay.d_b;
+  if (d.residual && r.block_in < 0)  // (a chain run ending inside a res_block: never planned)
+    return fail(TIC_EINVAL, "layer %s: residual input not in a workspace", d.name.c_str());
+  a.res = d.residual ? ps.ln.ws[r.block_in] : nullptr;
+  a.out = last_enc ? ps.d_pre : ps.ln.ws[r.dst];
+  a.qout = last_enc ? ps.d_idx : nullptr;
+  a.lut = h->d_lut;
+  a.H = a.W = lay.h_in;
+  a.Ho = a.Wo = lay.h_out;
+  a.pad_y = a.pad_x = same_pad(d.kind, lay.h_in);
+  a.qscale = (float)(h->Q - 1);
+  a.num_cus = h->num_cus;
+  a.grid_cap = h->persist_grid;
+  a.max_n = h->wino4_max_n;
+  if (h->tune_reps > 0 && !lay.tuned.count(tkey(h, lay, n))) {
+    // time every compiled tiling on the live buffers (re-launching is idempotent)
+    const auto cands = conv_candidates(s, layer_form(h, lay));
+    if (!cands.empty()) {
+      auto launch = [&](int v) {
+        a.wp = conv_weights(lay, cands[v]);
+        cands[v]->fn(a, n, st);
+        return true;
+      };
+      auto words = [&](int v) { return strf("th=%d ns=%d w=%d", cands[v]->th, cands[v]->nsplit, cands[v]->wlds); };
+      int best = -1;
+      int rc = time_variants(st, (int)cands.size(), h->tune_reps, launch, &best, d.name.c_str(), n, words);
+      if (rc) return rc;
+      e = cands[best];
+    }
+    lay.tuned[tkey(h, lay, n)] = e;
+  }
+  a.wp = conv_weights(lay, e);
+  if (!(li < 64 && (ps.probe_skip >> li & 1))) e->fn(a, n, st);
+  return TIC_OK;
+}
+
+// Run layers [l0, l1) for n patches: the launches plan_launches gives, in order.  A pass over
+// both halves of a codec ([0, L): tic_codec_device) reads the decoder's symbols from d_idx, and
+// runs the encoder's last and the decoder's first chain launch as one where the plan joins them.
 int run_layers(tic_handle* h, Lane& ln, int l0, int l1, const void* in, int n, uint8_t* d_idx, float* d_pre,
                uint8_t* d_rgb, float* d_f32, const Prof& prof) {
   hipStream_t const st = ln.stream;
-  float* const* ws = ln.ws;
   const int L = (int)h->layers.size();
-  int cur = -1;       // ws index holding the current activation (-1: external input)
-  int block_in = -1;  // ws index of the enclosing res_block's input
-  // timing probe only (results invalid): TIC_PROBE_SKIP = bit mask of plain-conv layers
-  // whose launch is left out, to price a group of layers inside the whole step
-  unsigned long long probe_skip = 0;
-  if (const char* s = getenv("TIC_PROBE_SKIP")) probe_skip = strtoull(s, nullptr, 0);
-  // the decoder's input: the symbols this same pass wrote, or the caller's
-  const void* const sym_in = !h->rmbe() && l0 < h->n_enc && l1 > h->n_enc ? (const void*)d_idx : in;
+  Pass ps{h, ln, in, !h->rmbe() && l0 < h->n_enc && l1 > h->n_enc ? (const void*)d_idx : in, n, d_idx, d_pre, d_rgb,
+          d_f32, 0};
+  if (const char* s = getenv("TIC_PROBE_SKIP")) ps.probe_skip = strtoull(s, nullptr, 0);
+  Rot r;
   int marked = -1;  // event pair open around the launch of layer mark_layer
   auto mark_close = [&]() -> int {
     if (marked >= 0) {
@@ -1040,7 +1455,8 @@ int run_layers(tic_handle* h, Lane& ln, int l0, int l1, const void* in, int n, u
     }
     return TIC_OK;
   };
-  for (int li = l0; li < l1; ++li) {
+  for (const Launch& p : plan_launches(h, l0, l1, !prof.ev && h->tune_reps == 0)) {
+    const int li = p.first;
     if (marked >= 0) {  // the marked launch was the last one enqueued
       if (int rc = mark_close()) return rc;
     }
@@ -1048,307 +1464,37 @@ int run_layers(tic_handle* h, Lane& ln, int l0, int l1, const void* in, int n, u
       marked = ln.mark_n;
       HIP_TRY(hipEventRecord(ln.mark_ev[2 * marked], st));
     }
-    LayerRT& lay = h->layers[li];
-    const LayerDef& d = lay.def;
-    const bool first = li == 0;
-    const bool last = li == L - 1;
-    const bool last_enc = !h->rmbe() && li == h->n_enc - 1;
-    const bool first_dec = !h->rmbe() && li == h->n_enc;
+    const LayerDef& d = h->layers[li].def;
     // choose the output buffer: any ws not holding the input or the res-block input
-    int dst = -1;
+    r.dst = -1;
     for (int b = 0; b < 3; ++b)
-      if (b != cur && b != block_in) {
-        dst = b;
+      if (b != r.cur && b != r.block_in) {
+        r.dst = b;
         break;
       }
     const bool starts_block = d.kind == K_S1 && !d.residual && li + 1 < L && h->layers[li + 1].def.residual;
-    if (starts_block) block_in = cur;
-    const float* src = cur >= 0 ? ws[cur] : nullptr;
+    if (starts_block) r.block_in = r.cur;
     if (prof.ev) HIP_TRY(hipEventRecord(prof.ev[2 * li], st));
-    const bool fuse = first && li + 1 < l1 && fuses01(h);
-    if (fuse) {
-      LayerRT& l1r = h->layers[1];
-      tic::Enc01Args a{};
-      a.in = in;
-      a.wp0 = lay.d_w;
-      a.b0 = lay.d_b;
-      a.wp1 = l1r.d_w;
-      a.b1 = l1r.d_b;
-      a.out = ws[dst];
-      a.H = a.W = lay.h_in;
-      a.H1 = a.W1 = lay.h_out;
-      a.H2 = a.W2 = l1r.h_out;
-      a.pad0y = a.pad0x = same_pad(d.kind, lay.h_in);
-      a.pad1y = a.pad1x = same_pad(K_S2, l1r.h_in);
-      a.nlut = h->d_nlut;
-      for (int c = 0; c < 3; ++c) {
-        a.mean[c] = h->mean[c];
-        a.std[c] = h->std[c];
-      }
-      if (getenv("TIC_ENC01_TIMING")) {  // phase timestamps (tools/chain_timing.py --enc01)
-        // sized for the largest grid of any variant (2-row tiles)
-        int rc2 = probe_stamps(ln, 2, n * ((l1r.h_out + 1) / 2) * ((l1r.h_out + 15) / 16), st, &a.tstamp);
-        if (rc2) return rc2;
-      }
-      auto it = lay.tuned_var.find(-n);  // fused-pair variants keyed by -n
-      int var = it != lay.tuned_var.end() ? it->second : tic::kEnc01Default;
-      if (const char* t = getenv("TIC_ENC01_VARIANT")) var = atoi(t);
-      else if (h->tune_reps > 0 && it == lay.tuned_var.end()) {
-        int rc = time_variants(st, tic::enc01_variants(), h->tune_reps,
-                               [&](int v) { return tic::launch_enc01(d.cout, l1r.def.cout, !h->rmbe(), a, n, st, v); },
-                               &var, "enc01", n);
-        if (rc) return rc;
-        lay.tuned_var[-n] = var;
-      }
-      if (!tic::launch_enc01(d.cout, l1r.def.cout, !h->rmbe(), a, n, st, var))
-        return fail(TIC_EUNSUPPORTED, "fused first layers %d->%d->%d not compiled", d.cin, d.cout, l1r.def.cout);
-      int rc = check_launch();
-      if (rc) return rc;
-      if (prof.ev) {
-        HIP_TRY(hipEventRecord(prof.ev[1], st));
-        HIP_TRY(hipEventRecord(prof.ev[2], st));  // layer 1 ran inside layer 0's launch
-        HIP_TRY(hipEventRecord(prof.ev[3], st));
-      }
-      cur = dst;
-      ++li;  // layer 1 consumed
-      continue;
+    int rc = TIC_OK;
+    switch (p.kind) {
+      case LK_ENC01: rc = enqueue_enc01(ps, r); break;
+      case LK_DEC10: rc = enqueue_dec10(ps, r); break;
+      case LK_CHAIN: rc = enqueue_chain(ps, r, p); break;
+      case LK_FIRST: rc = enqueue_first(ps, r); break;
+      case LK_LAST: rc = enqueue_last(ps, r); break;
+      case LK_CONV: rc = enqueue_conv(ps, r, li); break;
     }
-    if (li == L - 2 && li + 1 < l1 && fuses_tail(h)) {
-      LayerRT& last_l = h->layers[L - 1];
-      tic::Dec10Args a{};
-      a.in = src;
-      a.wp1 = lay.d_w;
-      a.w1raw = lay.d_w3;
-      a.b1 = lay.d_b;
-      a.H = a.W = lay.h_in;
-      a.rgb.wraw = last_l.d_w3;
-      a.rgb.bias = last_l.d_b;
-      a.rgb.out_u8 = d_rgb;
-      a.rgb.out_f32 = d_f32;
-      a.rgb.H = a.rgb.W = last_l.h_in;
-      a.rgb.num_cus = h->num_cus;
-      a.rgb.grid_cap = h->persist_grid;
-      for (int c = 0; c < 3; ++c) {
-        a.rgb.mean[c] = h->mean[c];
-        a.rgb.std[c] = h->std[c];
-      }
-      auto it = lay.tuned_var.find(n);  // fused-tail variants keyed by n on layer L-2
-      int var = it != lay.tuned_var.end() ? it->second : tic::kDec10Default;
-      if (const char* t = getenv("TIC_DEC10_VARIANT")) var = atoi(t);
-      else if (h->tune_reps > 0 && it == lay.tuned_var.end()) {
-        int rc = time_variants(st, tic::dec10_variants(), h->tune_reps,
-                               [&](int v) { return tic::launch_dec10(d.cin, d.cout, a, n, st, v); }, &var, "dec10", n);
-        if (rc) return rc;
-        lay.tuned_var[n] = var;
-      }
-      if (!tic::launch_dec10(d.cin, d.cout, a, n, st, var))
-        return fail(TIC_EUNSUPPORTED, "fused decoder tail %d->%d->3 not compiled", d.cin, d.cout);
-      int rc = check_launch();
-      if (rc) return rc;
-      if (prof.ev) {
-        HIP_TRY(hipEventRecord(prof.ev[2 * li + 1], st));
-        HIP_TRY(hipEventRecord(prof.ev[2 * li + 2], st));  // the last layer ran inside this launch
-        HIP_TRY(hipEventRecord(prof.ev[2 * li + 3], st));
-      }
-      break;
-    }
-    const ChainSpan sp = chain_span_at(h, li);
-    ChainSpan jd;  // the decoder-side launch joined to this one (tic_codec_device's pass)
-    const bool join = sp.valid() && !prof.ev && h->tune_reps == 0 && chain_join_at(h, li, &jd) && jd.last() < l1;
-    if (sp.valid() && sp.last() < l1) {
-      const int s1 = sp.s1, ce = sp.end, nl = ce - s1 + (join ? jd.end - jd.s1 : 0);
-      const ChainSpan& tsp = join ? jd : sp;  // the span that carries the tail
-      const int te = tsp.end;                 // the tail's layer
-      const LayerRT& lr = h->layers[s1];  // the run's first stride-1 layer
-      const bool first_dec_c = !h->rmbe() && s1 == h->n_enc;
-      const bool last_enc_c = !h->rmbe() && ce - 1 == h->n_enc - 1;
-      const int R = ((lr.h_in + 7) / 8) * ((lr.h_in + 7) / 8);  // 8x8 regions per patch
-      // hand-offs + 1 (joined: the junction is one more slot of the same protocol)
-      int rc = ensure_chain(h, ln, nl + (sp.head ? 1 : 0) + (tsp.tail ? 1 : 0), n, R);
-      if (rc) return rc;
-      tic::ChainArgs a{};
-      for (int k = 0; k < nl; ++k) {  // (joined: the decoder's run follows the encoder's, s1 + k)
-        const LayerRT& lk = h->layers[s1 + k];
-        a.layer[k] = {lk.d_ww, lk.d_b, lk.def.act, lk.def.residual};
-      }
-      a.nl = nl;
-      a.nq = join ? ce - s1 - 1 : -1;
-      a.in = first_dec_c ? sym_in : (const void*)src;
-      a.lut = h->d_lut;
-      a.out = last_enc_c ? d_pre : ws[dst];
-      a.qout = last_enc_c ? d_idx : nullptr;
-      a.qscale = (float)(h->Q - 1);
-      a.H = a.W = lr.h_in;
-      a.rh = a.rw = (lr.h_in + 7) / 8;
-      a.n = n;
-      a.xbuf = ln.xbuf;
-      a.flags = ln.cflags;
-      a.ctl = ln.ctl;
-      a.dispatch_order = chain_launch_order(h, n, R);
-      if (sp.head) {  // the stride-2 layer in front (layer li): its direct packing, input = src
-        a.head = {lay.d_w, lay.d_b, d.act, 0};
-        a.head_in = src;
-        a.hH = a.hW = lay.h_in;
-        a.hpad = same_pad(K_S2, lay.h_in);
-      }
-      if (tsp.tail) {  // the transposed layer behind (layer te), writing the next activation
-        const LayerRT& tl = h->layers[te];
-        a.tail = {tl.d_w, tl.d_b, tl.def.act, 0};
-        a.tail_out = ws[dst];
-      }
-      const bool tail2_pw = tsp.tail2 && layer_form(h, h->layers[te + 1]) == 1;
-      if (tsp.tail2) {  // and the next one (decode_2), whose output is the next activation instead;
-                       // in its polyphase Winograd form where the s2_form policy runs it so
-        const LayerRT& tl2 = h->layers[te + 1];
-        a.tail2 = {tail2_pw ? tl2.d_wp : tl2.d_w, tl2.d_b, tl2.def.act, 0};
-        a.tail2_out = ws[dst];
-      }
-      if (const char* pr = getenv("TIC_CHAIN_PROBE")) a.probe = atoi(pr);
-      if (getenv("TIC_CHAIN_TIMING")) {  // phase timestamps of this launch (tools/chain_timing.py)
-        int rc2 = probe_stamps(ln, first_dec_c || tsp.tail ? 1 : 0, n * R, st, &a.tstamp);
-        if (rc2) return rc2;
-      }
-      const int inm = first_dec_c ? tic::IN_IDX : tic::IN_F32, outm = last_enc_c ? tic::OUT_QUANT : tic::OUT_F32;
-      const int ht = (sp.head ? tic::CH_HEAD : 0) | (tsp.tail ? tic::CH_TAIL : 0) | (tsp.tail2 ? tic::CH_TAIL2 : 0) |
-                     (tail2_pw ? tic::CH_TAIL2_PW : 0) | (join ? tic::CH_JOIN : 0);
-      const int span_last = tsp.last();
-      if (!tic::launch_wino_chain(inm, outm, a, st, h->chain_wh, ht))
-        return fail(TIC_EUNSUPPORTED, "no chain kernel for layers %d..%d", li, span_last);
-      rc = check_launch();
-      if (rc) return rc;
-      if (prof.ev) {
-        HIP_TRY(hipEventRecord(prof.ev[2 * li + 1], st));
-        for (int k = li + 1; k <= span_last; ++k) {  // the other layers ran inside this launch
-          HIP_TRY(hipEventRecord(prof.ev[2 * k], st));
-          HIP_TRY(hipEventRecord(prof.ev[2 * k + 1], st));
-        }
-      }
-      block_in = -1;
-      cur = dst;
-      li = span_last;
-      continue;
-    }
-    if (first) {
-      tic::RgbInArgs a{};
-      a.in = in;
-      a.wp = lay.d_w;
-      a.bias = lay.d_b;
-      a.out = ws[dst];
-      a.H = a.W = lay.h_in;
-      a.Ho = a.Wo = lay.h_out;
-      a.pad_y = a.pad_x = same_pad(d.kind, lay.h_in);
-      for (int c = 0; c < 3; ++c) {
-        a.mean[c] = h->mean[c];
-        a.std[c] = h->std[c];
-      }
-      auto it = lay.tuned_var.find(n);
-      int var = it != lay.tuned_var.end() ? it->second : kRgbInDefault;
-      if (h->tune_reps > 0 && it == lay.tuned_var.end()) {
-        int rc = time_variants(st, tic::rgb_in_variants(), h->tune_reps,
-                               [&](int v) { return tic::launch_rgb_in(d.cout, !h->rmbe(), a, n, st, v); }, &var,
-                               "rgb_in", n);
-        if (rc) return rc;
-        lay.tuned_var[n] = var;
-      }
-      if (!tic::launch_rgb_in(d.cout, !h->rmbe(), a, n, st, var))
-        return fail(TIC_EUNSUPPORTED, "first layer %s: width %d not compiled", d.name.c_str(), d.cout);
-    } else if (last) {
-      tic::RgbOutArgs a{};
-      a.in = src;
-      a.wp = lay.d_w;
-      a.wp2 = lay.d_w2;
-      a.wraw = lay.d_w3;
-      a.num_cus = h->num_cus;
-      a.grid_cap = h->persist_grid;
-      a.bias = lay.d_b;
-      a.out_u8 = d_rgb;
-      a.out_f32 = d_f32;
-      a.H = a.W = lay.h_in;
-      for (int c = 0; c < 3; ++c) {
-        a.mean[c] = h->mean[c];
-        a.std[c] = h->std[c];
-      }
-      const RgbOutForm fm = rgb_out_form();
-      auto it = lay.tuned_var.find(n);
-      int var = rgb_out_variant(lay.tuned_var, n);
-      if (h->tune_reps > 0 && (it == lay.tuned_var.end() || !fm.has(it->second)) && !getenv("TIC_RGB_OUT_TILE")) {
-        int rc = time_variants(st, fm.hi - fm.lo, h->tune_reps,
-                               [&](int v) { return tic::launch_rgb_out(d.cin, a, n, st, fm.lo + v); }, &var,
-                               "rgb_out", n);
-        if (rc) return rc;
-        var += fm.lo;
-        lay.tuned_var[n] = var;
-      }
-      if (!tic::launch_rgb_out(d.cin, a, n, st, var))
-        return fail(TIC_EUNSUPPORTED, "last layer %s: width %d not compiled", d.name.c_str(), d.cin);
-    } else {
-      const int inm = first_dec ? tic::IN_IDX : tic::IN_F32;
-      const int outm = last_enc ? tic::OUT_QUANT : tic::OUT_F32;
-      const int hg = d.kind == K_T2 ? lay.h_in : lay.h_out;
-      const tic::ConvEntry* e = nullptr;
-      auto it = lay.tuned.find(tkey(h, lay, n));
-      if (it != lay.tuned.end() && wino4_fits(*it->second, hg, hg)) e = it->second;
-      else e = find_conv(d.kind, d.cin, d.cout, d.act, d.residual, inm, outm, hg, hg, n, layer_form(h, lay));
-      if (!e)
-        return fail(TIC_EUNSUPPORTED, "no kernel for layer %s (kind %d %d->%d act %d res %d in %d out %d)",
-                    d.name.c_str(), d.kind, d.cin, d.cout, d.act, d.residual, inm, outm);
-      tic::ConvArgs a{};
-      a.in = first_dec ? sym_in : (const void*)src;
-      a.wp = lay.d_w;
-      a.bias = lay.d_b;
-      if (d.residual && block_in < 0)  // (a chain run ending inside a res_block: never planned)
-        return fail(TIC_EINVAL, "layer %s: residual input not in a workspace", d.name.c_str());
-      a.res = d.residual ? ws[block_in] : nullptr;
-      a.out = last_enc ? d_pre : ws[dst];
-      a.qout = last_enc ? d_idx : nullptr;
-      a.lut = h->d_lut;
-      a.H = a.W = lay.h_in;
-      a.Ho = a.Wo = lay.h_out;
-      a.pad_y = a.pad_x = same_pad(d.kind, lay.h_in);
-      a.qscale = (float)(h->Q - 1);
-      a.num_cus = h->num_cus;
-      a.grid_cap = h->persist_grid;
-      a.max_n = h->wino4_max_n;
-      if (h->tune_reps > 0 && it == lay.tuned.end()) {
-        // time every compiled tiling on the live buffers (re-launching is idempotent)
-        auto cands = conv_candidates(d.kind, d.cin, d.cout, d.act, d.residual, inm, outm, layer_form(h, lay), hg, hg);
-        Event t0, t1;
-        HIP_TRY(t0.create());
-        HIP_TRY(t1.create());
-        std::vector<std::vector<float>> samples(cands.size());
-        const bool log = getenv("TIC_TUNE_LOG") != nullptr;
-        for (int pass = 0; pass < kSoloPasses; ++pass) {
-          for (size_t ci = 0; ci < cands.size(); ++ci) {
-            const tic::ConvEntry* c = cands[ci];
-            a.wp = conv_weights(lay, c);
-            c->fn(a, n, st);  // warm
-            HIP_TRY(hipEventRecord(t0.e, st));
-            for (int r = 0; r < h->tune_reps; ++r) c->fn(a, n, st);
-            HIP_TRY(hipEventRecord(t1.e, st));
-            HIP_TRY(hipEventSynchronize(t1.e));
-            float ms = 0.f;
-            HIP_TRY(hipEventElapsedTime(&ms, t0.e, t1.e));
-            if (log)
-              fprintf(stderr, "tune %-22s n=%d th=%d ns=%d w=%d : %.2f us\n", d.name.c_str(), n, c->th, c->nsplit,
-                      c->wlds, 1e3f * ms / h->tune_reps);
-            samples[ci].push_back(ms);
-          }
-        }
-        std::vector<std::pair<const tic::ConvEntry*, float>> timed;
-        for (size_t ci = 0; ci < cands.size(); ++ci) timed.emplace_back(cands[ci], median_of(samples[ci]));
-        if (!timed.empty()) e = pick_with_ties(timed, e);
-        int rc = check_launch();
-        if (rc) return rc;
-        lay.tuned[tkey(h, lay, n)] = e;
-      }
-      a.wp = conv_weights(lay, e);
-      if (!(li < 64 && (probe_skip >> li & 1))) e->fn(a, n, st);
-    }
-    int rc = check_launch();
+    if (!rc) rc = check_launch();
     if (rc) return rc;
-    if (prof.ev) HIP_TRY(hipEventRecord(prof.ev[2 * li + 1], st));
-    if (d.residual) block_in = -1;
-    cur = dst;
+    if (prof.ev) {
+      HIP_TRY(hipEventRecord(prof.ev[2 * li + 1], st));
+      for (int k = li + 1; k <= p.last; ++k) {  // the other layers ran inside this launch
+        HIP_TRY(hipEventRecord(prof.ev[2 * k], st));
+        HIP_TRY(hipEventRecord(prof.ev[2 * k + 1], st));
+      }
+    }
+    if (p.kind == LK_CHAIN || d.residual) r.block_in = -1;
+    r.cur = r.dst;
   }
   return mark_close();
 }
@@ -1472,7 +1618,7 @@ int decode_dev(tic_handle* h, const uint8_t* idx, int n, uint8_t* rgb, float* f3
 int codec_dev(tic_handle* h, const uint8_t* in, int n, uint8_t* idx, uint8_t* rgb) {
   const size_t pp = (size_t)h->P * h->P * 3, ce = code_elems(h);
   const PatchBuf bufs[3] = {{in, pp, false}, {idx, ce, true}, {rgb, pp, true}};
-  const bool joined = h->tune_reps == 0 && codec_join_start(h) >= 0;
+  const bool joined = h->tune_reps == 0 && plan_joined(h);
   for (int s = 0; s < n; s += h->chunk) {
     const int m = std::min(h->chunk, n - s);
     int rc = run_chunk(h, s, m, h->tune_reps == 0, bufs, 3, [&](Lane& ln, int o, int k) {
@@ -1506,6 +1652,25 @@ int rmbe_dev(tic_handle* h, const float* in, int n, float* out, const Prof& prof
   }
   return TIC_OK;
 }
+
+// Device scratch of a measured step of n patches: its symbols, and its output (u8 patches, or
+// the rmbe net's f32 windows).
+struct StepScratch {
+  Scratch idx, out;
+  int alloc(const tic_handle* h, int n) {
+    const size_t ce = h->rmbe() ? 0 : (size_t)n * code_elems(h);
+    const size_t px = (size_t)n * h->P * h->P * 3;
+    HIP_TRY(idx.alloc(std::max<size_t>(ce, 16)));
+    HIP_TRY(out.alloc(px * (h->rmbe() ? 4 : 1)));
+    return TIC_OK;
+  }
+  // the step as its per-half entries run it (never joined): encode then decode, or the rmbe net
+  int run_halves(tic_handle* h, const void* d_in, int n, const Prof& prof) {
+    if (h->rmbe()) return rmbe_dev(h, (const float*)d_in, n, (float*)out.p, prof);
+    int rc = encode_dev(h, (const uint8_t*)d_in, n, (uint8_t*)idx.p, nullptr, prof);
+    return rc ? rc : decode_dev(h, (const uint8_t*)idx.p, n, (uint8_t*)out.p, nullptr, prof);
+  }
+};
 
 int fill_layer_info(const LayerDef& d, char* name_buf, int name_len, int* kind, int* cin, int* cout, int* act,
                     int* stage, int* residual) {
@@ -2175,19 +2340,10 @@ int tic_profile_layers(tic_handle* h, const void* d_in, int n, int iters, float*
     ev[i] = evs[i].e;
   }
   std::vector<double> acc(L, 0.0);
-  const size_t ce = h->rmbe() ? 0 : (size_t)n * code_elems(h);
-  const size_t px = (size_t)n * h->P * h->P * 3;
-  Scratch s_idx, s_out;
-  HIP_TRY(s_idx.alloc(std::max<size_t>(ce, 16)));
-  HIP_TRY(s_out.alloc(px * (h->rmbe() ? 4 : 1)));
-  void *d_idx = s_idx.p, *d_out = s_out.p;
+  StepScratch scratch;
+  if ((rc = scratch.alloc(h, n))) return rc;
   for (int it = 0; it < iters && rc == TIC_OK; ++it) {
-    if (h->rmbe()) {
-      rc = rmbe_dev(h, (const float*)d_in, n, (float*)d_out, Prof{ev.data()});
-    } else {
-      rc = encode_dev(h, (const uint8_t*)d_in, n, (uint8_t*)d_idx, nullptr, Prof{ev.data()});
-      if (!rc) rc = decode_dev(h, (const uint8_t*)d_idx, n, (uint8_t*)d_out, nullptr, Prof{ev.data()});
-    }
+    rc = scratch.run_halves(h, d_in, n, Prof{ev.data()});
     if (rc) break;
     hipError_t e = hipStreamSynchronize(h->stream);
     if (e != hipSuccess) rc = fail(TIC_EHIP, "profile sync: %s", hipGetErrorString(e));
@@ -2213,19 +2369,10 @@ int tic_autotune(tic_handle* h, const void* d_in, int n, int reps) {
     l.tuned_var.erase(-n);
   }
   clear_graphs(h);
-  const size_t ce = h->rmbe() ? 0 : (size_t)n * code_elems(h);
-  const size_t px = (size_t)n * h->P * h->P * 3;
-  Scratch s_idx, s_out;
-  HIP_TRY(s_idx.alloc(std::max<size_t>(ce, 16)));
-  HIP_TRY(s_out.alloc(px * (h->rmbe() ? 4 : 1)));
-  void *d_idx = s_idx.p, *d_out = s_out.p;
+  StepScratch scratch;
+  if ((rc = scratch.alloc(h, n))) return rc;
   h->tune_reps = reps;
-  if (h->rmbe()) {
-    rc = rmbe_dev(h, (const float*)d_in, n, (float*)d_out, Prof{nullptr});
-  } else {
-    rc = encode_dev(h, (const uint8_t*)d_in, n, (uint8_t*)d_idx, nullptr, Prof{nullptr});
-    if (!rc) rc = decode_dev(h, (const uint8_t*)d_idx, n, (uint8_t*)d_out, nullptr, Prof{nullptr});
-  }
+  rc = scratch.run_halves(h, d_in, n, Prof{nullptr});
   h->tune_reps = 0;
   hipError_t e = hipStreamSynchronize(h->stream);
   if (rc) return rc;
@@ -2250,15 +2397,16 @@ int tic_autotune_step(tic_handle* h, const void* d_in, int n, int rounds, int re
     sizes.push_back((n + k - 1) / k);
     if (n % k) sizes.push_back(n / k);
   }
-  // make sure every layer has a solo-tuned starting point for those sizes
+  const int L = (int)h->layers.size();
+  // make sure every launch with a choice (a chain launch has none) has a solo-tuned starting
+  // point for those sizes, under the key tic_autotune stores it
   for (int m : sizes) {
     bool have = true;
-    for (size_t i = 0; i < h->layers.size(); ++i) {
-      const LayerRT& l = h->layers[i];
-      const bool rgb = i == 0 || i + 1 == h->layers.size();
-      if (i + 2 >= h->layers.size() && fuses_tail(h)) continue;  // runs inside dec10_kernel
-      if (in_chain(h, (int)i)) continue;                          // runs inside wino_chain_kernel
-      if (rgb ? !l.tuned_var.count(m) : !l.tuned.count(tkey(h, l, m))) have = false;
+    for (const Launch& p : plan_launches(h, 0, L, false)) {
+      const LayerRT& l = h->layers[p.first];
+      if (p.kind == LK_CONV ? !l.tuned.count(tkey(h, l, m))
+                            : p.kind != LK_CHAIN && !l.tuned_var.count(p.kind == LK_ENC01 ? -m : m))
+        have = false;
     }
     if (!have) {
       rc = tic_autotune(h, d_in, m, reps);
@@ -2266,12 +2414,9 @@ int tic_autotune_step(tic_handle* h, const void* d_in, int n, int rounds, int re
     }
   }
   clear_graphs(h);
-  const size_t ce = h->rmbe() ? 0 : (size_t)n * code_elems(h);
-  const size_t px = (size_t)n * h->P * h->P * 3;
-  Scratch s_idx, s_out;
-  HIP_TRY(s_idx.alloc(std::max<size_t>(ce, 16)));
-  HIP_TRY(s_out.alloc(px * (h->rmbe() ? 4 : 1)));
-  void *d_idx = s_idx.p, *d_out = s_out.p;
+  StepScratch scratch;
+  if ((rc = scratch.alloc(h, n))) return rc;
+  void *d_idx = scratch.idx.p, *d_out = scratch.out.p;
   Event ev0, ev1;
   HIP_TRY(ev0.create());
   HIP_TRY(ev1.create());
@@ -2367,9 +2512,10 @@ int tic_autotune_step(tic_handle* h, const void* d_in, int n, int rounds, int re
     *cur_ms = *keep ? ra[kPairs / 2] : rb[kPairs / 2];
     return TIC_OK;
   };
-  // test hooks (tests/test_gpu_tuning.py): "flip" accepts every structural alternative (the
-  // fusions and the chain switch state whatever they measure), "nowin" lets no per-layer
-  // candidate win — together they reach layers that were never tuned and keep no candidate
+  // test hooks (tests/test_gpu_wino4.py::test_autotune_step_untuned_layers_keep_kernels): "flip"
+  // accepts every structural alternative (the fusions and the chain switch state whatever they
+  // measure), "nowin" lets no per-layer candidate win — together they reach layers that were
+  // never tuned and keep no candidate
   const char* tt = getenv("TIC_TUNE_STEP_TEST");
   const bool t_flip = tt && strstr(tt, "flip"), t_nowin = tt && strstr(tt, "nowin");
   // A fresh GPU runs its first ≈ 60 steps below its steady clock: steps for
@@ -2467,7 +2613,7 @@ int tic_autotune_step(tic_handle* h, const void* d_in, int n, int rounds, int re
   if (!rc && h->chain && !getenv("TIC_CHAIN_J")) {  // the two chain launches of the step joined at the quantiser
     const int was = h->chain_j;
     h->chain_j = 1;
-    const bool can = codec_join_start(h) >= 0;
+    const bool can = plan_joined(h);
     h->chain_j = was;
     if (can && t_flip) {
       h->chain_j = !was;
@@ -2478,104 +2624,85 @@ int tic_autotune_step(tic_handle* h, const void* d_in, int n, int rounds, int re
       clear_graphs(h);
     }
   }
-  const int L = (int)h->layers.size();
-  for (int round = 0; round < rounds && !rc; ++round) {
-    for (int i = 0; i < L && !rc; ++i) {
-      LayerRT& l = h->layers[i];
-      const LayerDef& d = l.def;
-      const bool first = i == 0, last = i == L - 1;
-      if (i == 1 && fuses01(h)) continue;
-      if (i == L - 1 && fuses_tail(h)) continue;
-      if (in_chain(h, i)) continue;
-      // the fused pairs' variants: dec10_kernel keyed by n on layer L-2, enc01_kernel by -n
-      // on layer 0
-      const bool tail = i == L - 2 && fuses_tail(h), pair = first && fuses01(h);
-      if (tail || pair) {
-        if (getenv(tail ? "TIC_DEC10_VARIANT" : "TIC_ENC01_VARIANT")) continue;
-        const int sg = tail ? 1 : -1;
-        auto iv = l.tuned_var.find(sg * sizes[0]);
-        const int keep = iv != l.tuned_var.end() ? iv->second : tail ? tic::kDec10Default : tic::kEnc01Default;
-        int best_v = keep;
-        float best = cur;
-        for (int v = 0; v < (tail ? tic::dec10_variants() : tic::enc01_variants()) && !rc; ++v) {
-          if (v == keep) continue;
-          for (int m : sizes) l.tuned_var[sg * m] = v;
-          float ms = 0.f;
-          rc = measure(&ms);
-          if (log) fprintf(stderr, "tune-step %s variant %d : %.2f us\n", tail ? "dec10" : "enc01", v, 1e3f * ms);
-          if (!rc && ms < best * (1.f - kSweepMargin)) {
-            best = ms;
-            best_v = v;
-          }
-        }
-        auto put = [&](int v) {
-          for (int m : sizes) l.tuned_var[sg * m] = v;
-        };
-        put(keep);
-        bool sw = false;
-        if (!rc && best_v != keep)
-          rc = confirm([&](bool alt) { put(alt ? best_v : keep); }, kLayerMargin, tail ? "dec10" : "enc01", &sw, &cur);
-        continue;
+  // One launch's choice by the whole step: every candidate but the current one (`keep`) is
+  // installed with put() and the step measured; the best of them, if it beat the step so far by
+  // kSweepMargin (and the "nowin" hook is not set for it), meets `keep` in the confirmed A/B.
+  // words(c): how the log names candidate c.
+  auto sweep = [&](const auto& cands, auto keep, const auto& put, const auto& words, const char* label, bool nowin) {
+    auto best_c = keep;
+    float best = cur;
+    for (const auto& c : cands) {
+      if (c == keep || rc) continue;
+      put(c);
+      float ms = 0.f;
+      rc = measure(&ms);
+      if (log) fprintf(stderr, "tune-step %s : %.2f us\n", words(c).c_str(), 1e3f * ms);
+      if (!rc && ms < best * (1.f - kSweepMargin) && !nowin) {
+        best = ms;
+        best_c = c;
       }
-      if (first || last) {
-        const RgbOutForm fm = first ? RgbOutForm{0, tic::rgb_in_variants()} : rgb_out_form();
-        auto iv = l.tuned_var.find(sizes[0]);
-        const int keep = first ? (iv != l.tuned_var.end() ? iv->second : kRgbInDefault)
-                               : rgb_out_variant(l.tuned_var, sizes[0]);
-        int best_v = keep;
-        float best = cur;
-        for (int v = fm.lo; v < fm.hi && !rc; ++v) {
-          if (v == keep) continue;
-          for (int m : sizes) l.tuned_var[m] = v;
-          float ms = 0.f;
-          rc = measure(&ms);
-          if (log) fprintf(stderr, "tune-step %-22s variant %d : %.2f us\n", d.name.c_str(), v, 1e3f * ms);
-          if (!rc && ms < best * (1.f - kSweepMargin)) {
-            best = ms;
-            best_v = v;
-          }
+    }
+    put(keep);
+    bool sw = false;
+    if (!rc && best_c != keep)
+      rc = confirm([&](bool alt) { put(alt ? best_c : keep); }, kLayerMargin, label, &sw, &cur);
+  };
+  auto range = [](int lo, int hi) {
+    std::vector<int> v;
+    for (int i = lo; i < hi; ++i) v.push_back(i);
+    return v;
+  };
+  for (int round = 0; round < rounds && !rc; ++round) {
+    for (const Launch& p : plan_launches(h, 0, L, true)) {
+      if (rc) break;
+      LayerRT& l = h->layers[p.first];
+      const char* name = l.def.name.c_str();
+      const int m0 = sizes[0];
+      switch (p.kind) {
+        case LK_CHAIN: break;  // a chain launch has one instance
+        case LK_ENC01:
+        case LK_DEC10: {  // the fused pairs' variants: dec10_kernel keyed by n on layer L-2, enc01_kernel by -n
+                          // on layer 0
+          const bool tail = p.kind == LK_DEC10;
+          if (getenv(tail ? "TIC_DEC10_VARIANT" : "TIC_ENC01_VARIANT")) break;
+          const int sg = tail ? 1 : -1;
+          const char* label = tail ? "dec10" : "enc01";
+          auto put = [&](int v) {
+            for (int m : sizes) l.tuned_var[sg * m] = v;
+          };
+          sweep(range(0, tail ? tic::dec10_variants() : tic::enc01_variants()),
+                tail ? dec10_variant(h, m0) : enc01_variant(h, m0), put,
+                [&](int v) { return strf("%s variant %d", label, v); }, label, false);
+          break;
         }
-        auto put = [&](int v) {
-          for (int m : sizes) l.tuned_var[m] = v;
-        };
-        put(keep);
-        bool sw = false;
-        if (!rc && best_v != keep)
-          rc = confirm([&](bool alt) { put(alt ? best_v : keep); }, kLayerMargin, d.name.c_str(), &sw, &cur);
-      } else {
-        const bool last_enc = !h->rmbe() && i == h->n_enc - 1, first_dec = !h->rmbe() && i == h->n_enc;
-        const int hg = d.kind == K_T2 ? l.h_in : l.h_out;
-        auto cands = conv_candidates(d.kind, d.cin, d.cout, d.act, d.residual, first_dec ? tic::IN_IDX : tic::IN_F32,
-                                     last_enc ? tic::OUT_QUANT : tic::OUT_F32, layer_form(h, l), hg, hg);
-        // an untuned size runs find_conv's pick: `keep` is then null and, when no candidate beats
-        // the current step, the size stays untuned (not a null entry, which would drop the layer)
-        auto kt = l.tuned.find(tkey(h, l, sizes[0]));
-        const tic::ConvEntry* keep = kt != l.tuned.end() ? kt->second : nullptr;
-        const tic::ConvEntry* best_e = keep;
-        float best = cur;
-        for (const tic::ConvEntry* c : cands) {
-          if (c == keep || rc) continue;
-          for (int m : sizes) l.tuned[tkey(h, l, m)] = c;
-          float ms = 0.f;
-          rc = measure(&ms);
-          if (log)
-            fprintf(stderr, "tune-step %-22s th=%d ns=%d w=%d : %.2f us\n", d.name.c_str(), c->th, c->nsplit,
-                    c->wlds, 1e3f * ms);
-          if (!rc && ms < best * (1.f - kSweepMargin) && !t_nowin) {
-            best = ms;
-            best_e = c;
-          }
+        case LK_FIRST:
+        case LK_LAST: {
+          const bool first = p.kind == LK_FIRST;
+          const RgbOutForm fm = first ? RgbOutForm{0, tic::rgb_in_variants()} : rgb_out_form();
+          auto put = [&](int v) {
+            for (int m : sizes) l.tuned_var[m] = v;
+          };
+          sweep(range(fm.lo, fm.hi), first ? rgb_in_variant(h, m0) : rgb_out_variant(h, m0), put,
+                [&](int v) { return strf("%-22s variant %d", name, v); }, name, false);
+          break;
         }
-        auto put = [&](const tic::ConvEntry* e) {
-          for (int m : sizes) {
-            if (e) l.tuned[tkey(h, l, m)] = e;
-            else l.tuned.erase(tkey(h, l, m));
-          }
-        };
-        put(keep);
-        bool sw = false;
-        if (!rc && best_e != keep)
-          rc = confirm([&](bool alt) { put(alt ? best_e : keep); }, kLayerMargin, d.name.c_str(), &sw, &cur);
+        case LK_CONV: {
+          // an untuned size runs find_conv's pick: `keep` is then null and, when no candidate beats
+          // the current step, the size stays untuned (not a null entry, which would drop the layer)
+          auto kt = l.tuned.find(tkey(h, l, m0));
+          const tic::ConvEntry* keep = kt != l.tuned.end() ? kt->second : nullptr;
+          auto put = [&](const tic::ConvEntry* e) {
+            for (int m : sizes) {
+              if (e) l.tuned[tkey(h, l, m)] = e;
+              else l.tuned.erase(tkey(h, l, m));
+            }
+          };
+          auto words = [&](const tic::ConvEntry* c) {
+            return strf("%-22s th=%d ns=%d w=%d", name, c->th, c->nsplit, c->wlds);
+          };
+          sweep(conv_candidates(conv_sig(h, p.first), layer_form(h, l)), keep, put, words, name, t_nowin);
+          break;
+        }
       }
     }
     if (log && !rc) fprintf(stderr, "tune-step n=%d after round %d: %.2f us\n", n, round + 1, 1e3f * cur);
@@ -2591,133 +2718,55 @@ int tic_layer_variant(const tic_handle* h, int i, int n, int* th, int* nsplit) {
   // nsplit reports (channel split) + 100 * (weights via LDS)
   if (i < 0 || i >= (int)h->layers.size()) return fail(TIC_EINVAL, "layer index %d out of range", i);
   *th = *nsplit = 0;
-  const LayerRT& l = h->layers[i];
   const int L = (int)h->layers.size();
   if (i == 0 || i == L - 1) {
-    auto iv = l.tuned_var.find(n);
-    const int v = i == 0 ? (iv != l.tuned_var.end() ? iv->second : kRgbInDefault) : rgb_out_variant(l.tuned_var, n);
+    const int v = i == 0 ? rgb_in_variant(h, n) : rgb_out_variant(h, n);
     static const int th_in[3] = {4, 8, 16}, th_out[12] = {4, 8, 16, 4, 8, 16, 4, 8, 16, 4, 8, 16};
     *th = i == 0 ? th_in[v] : th_out[v];
     *nsplit = i == L - 1 ? v / 3 : 0;  // last layer: 0 dense, 1 scatter, 2 VALU, 3 VALU persistent
     return TIC_OK;
   }
-  auto it = l.tuned.find(tkey(h, l, n));
-  const tic::ConvEntry* e = nullptr;
-  const int hg = l.def.kind == K_T2 ? l.h_in : l.h_out;
-  if (it != l.tuned.end() && wino4_fits(*it->second, hg, hg)) {
-    e = it->second;
-  } else {
-    const LayerDef& d = l.def;
-    const bool last_enc = !h->rmbe() && i == h->n_enc - 1, first_dec = !h->rmbe() && i == h->n_enc;
-    e = find_conv(d.kind, d.cin, d.cout, d.act, d.residual, first_dec ? tic::IN_IDX : tic::IN_F32,
-                  last_enc ? tic::OUT_QUANT : tic::OUT_F32, hg, hg, n, layer_form(h, l));
-  }
-  if (e) {
+  if (const tic::ConvEntry* e = pick_conv(h, i, n)) {
     *th = e->th;
     *nsplit = e->nsplit + 100 * e->wlds;
   }
   return TIC_OK;
 }
 
-int tic_layer_kernel(const tic_handle* h, int i, int n, char* name, int cap) {
-  if (!h || !name || cap <= 0) return fail(TIC_EINVAL, "null argument");
-  if (i < 0 || i >= (int)h->layers.size()) return fail(TIC_EINVAL, "layer index %d out of range", i);
-  const LayerRT& l = h->layers[i];
-  const LayerDef& d = l.def;
-  const int L = (int)h->layers.size();
-  const char* tf[2] = {"false", "true"};
+// Names the launch of `plan` that starts at layer i ('' for a layer inside a launch).
+static int name_launch_at(const tic_handle* h, const std::vector<Launch>& plan, int i, int n, char* name, int cap) {
   char buf[160] = "";
-  ChainSpan cs;  // the chain launch containing layer i
-  for (const ChainSpan& sp : chain_spans(h))
-    if (sp.start <= i && i <= sp.last()) cs = sp;
-  if (cs.valid()) {
-    if (cs.start == i) {
-      const bool first_dec = !h->rmbe() && cs.s1 == h->n_enc, last_enc = !h->rmbe() && cs.end - 1 == h->n_enc - 1;
-      const int ht = (cs.head ? tic::CH_HEAD : 0) | (cs.tail ? tic::CH_TAIL : 0) | (cs.tail2 ? tic::CH_TAIL2 : 0) |
-                     (cs.tail2 && layer_form(h, h->layers[cs.end + 1]) == 1 ? tic::CH_TAIL2_PW : 0);
-      snprintf(buf, sizeof buf, "wino_chain_kernel<%d,%d,%d,%d>", first_dec ? 1 : 0, last_enc ? 1 : 0, h->chain_wh,
-               ht);
+  for (const Launch& p : plan)
+    if (p.first == i) {
+      int rc = launch_name(h, p, n, buf, sizeof buf);
+      if (rc) return rc;
     }
-  } else if (fuses_tail(h) && i >= L - 2) {
-    if (i == L - 2) {
-      auto iv = l.tuned_var.find(n);
-      int v = iv != l.tuned_var.end() ? iv->second : tic::kDec10Default;
-      if (const char* t = getenv("TIC_DEC10_VARIANT")) v = atoi(t);
-      snprintf(buf, sizeof buf, "dec10_kernel<%d,%d,false,%d,0,%d,%s,%s>", d.cin, d.cout, (v & 2) ? 5 : 2,
-               (v & 4) ? 8 : 4, tf[(v >> 3) & 1], tf[!(v & 1)]);
-    }
-  } else if (fuses01(h) && (i == 0 || i == 1)) {
-    if (i == 0) {  // layer 1 runs inside layer 0's launch: empty name
-      auto iv = l.tuned_var.find(-n);
-      int v = iv != l.tuned_var.end() ? iv->second : tic::kEnc01Default;
-      if (const char* t = getenv("TIC_ENC01_VARIANT")) v = atoi(t);
-      static const int th1[5] = {2, 4, 2, 4, 8};
-      snprintf(buf, sizeof buf, "enc01_kernel<%d,%d,%d,%s,%s,%s>", d.cout, h->layers[1].def.cout, th1[v % 5],
-               tf[!h->rmbe()], tf[v >= 2], tf[getenv("TIC_ENC01_TIMING") != nullptr]);
-    }
-  } else if (i == 0 || i == L - 1) {
-    auto iv = l.tuned_var.find(n);
-    const int v = i == 0 ? (iv != l.tuned_var.end() ? iv->second : kRgbInDefault) : rgb_out_variant(l.tuned_var, n);
-    static const int th[3] = {4, 8, 16}, tw[3] = {64, 32, 16};
-    if (i == 0)
-      snprintf(buf, sizeof buf, "conv_rgb_s2_kernel<%d,%d,%s>", d.cout, th[v % 3], tf[!h->rmbe()]);
-    else if (v >= 6)
-      snprintf(buf, sizeof buf, "%s<%d,%d>", v >= 9 ? "convT_rgb_valu_persist_kernel" : "convT_rgb_valu_kernel", d.cin,
-               tw[v % 3]);
-    else
-      snprintf(buf, sizeof buf, "%s<%d,%d>", v >= 3 ? "convT_rgb_scatter_kernel" : "convT_rgb_kernel", d.cin,
-               th[v % 3]);
-  } else {
-    const bool last_enc = !h->rmbe() && i == h->n_enc - 1, first_dec = !h->rmbe() && i == h->n_enc;
-    const int hg = d.kind == K_T2 ? l.h_in : l.h_out;
-    auto it = l.tuned.find(tkey(h, l, n));
-    const tic::ConvEntry* e =
-        it != l.tuned.end() && wino4_fits(*it->second, hg, hg)
-            ? it->second
-            : find_conv(d.kind, d.cin, d.cout, d.act, d.residual, first_dec ? tic::IN_IDX : tic::IN_F32,
-                                        last_enc ? tic::OUT_QUANT : tic::OUT_F32, hg, hg, n, layer_form(h, l));
-    if (!e) return fail(TIC_EUNSUPPORTED, "layer %d has no compiled kernel", i);
-    if (e->wlds == 6)
-      snprintf(buf, sizeof buf, "conv3x3_pwino_kernel<%d,%d,%d,%d,%d,%s,%d,%d>", e->mode, e->cin, e->cout, e->wr,
-               e->act, tf[e->res != 0], e->in, e->out);
-    else if (e->wlds == 5)
-      snprintf(buf, sizeof buf, "conv3x3_wino4_kernel<%d,%d,%d,%d,%s,%d,%d>", e->cin, e->cout, e->th / 4, e->act,
-               tf[e->res != 0], e->in, e->out);
-    else if (e->wlds == 4)
-      snprintf(buf, sizeof buf, "conv3x3_wino_kernel<%d,%d,%d,%d,%d,%d,%s,%d,%d>", e->cin, e->cout, e->th / 2, e->wr,
-               e->nsplit, e->act, tf[e->res != 0], e->in, e->out);
-    else
-      snprintf(buf, sizeof buf, "conv3x3<%d,%d,%d,%d,%d,%d,%d,%d,%s,%d,%d>", e->mode, e->cin, e->cout, e->th,
-               e->wr, e->nsplit, e->wlds, e->act, tf[e->res != 0], e->in, e->out);
-  }
   const int len = (int)strlen(buf);
   if (len + 1 > cap) return fail(TIC_EINVAL, "name buffer too small (%d < %d)", cap, len + 1);
   memcpy(name, buf, len + 1);
   return TIC_OK;
 }
 
+// what tic_encode_device / tic_decode_device (or the rmbe entry) launch: the plan of the pass
+// that contains layer i, never joined
+int tic_layer_kernel(const tic_handle* h, int i, int n, char* name, int cap) {
+  if (!h || !name || cap <= 0) return fail(TIC_EINVAL, "null argument");
+  const int L = (int)h->layers.size();
+  if (i < 0 || i >= L) return fail(TIC_EINVAL, "layer index %d out of range", i);
+  const int l0 = h->rmbe() || i < h->n_enc ? 0 : h->n_enc, l1 = h->rmbe() || i >= h->n_enc ? L : h->n_enc;
+  return name_launch_at(h, plan_launches(h, l0, l1, false), i, n, name, cap);
+}
+
+// what tic_codec_device launches: one pass over both halves, joined where the plan says so
 int tic_codec_kernel(const tic_handle* h, int i, int n, char* name, int cap) {
   if (!h || !name || cap <= 0) return fail(TIC_EINVAL, "null argument");
-  if (i < 0 || i >= (int)h->layers.size()) return fail(TIC_EINVAL, "layer index %d out of range", i);
-  const int js = h->tune_reps == 0 ? codec_join_start(h) : -1;
-  ChainSpan jd;
-  if (js < 0 || !chain_join_at(h, js, &jd) || i < js || i > jd.last()) return tic_layer_kernel(h, i, n, name, cap);
-  char buf[160] = "";  // layers inside the joined launch: empty, as inside any fused launch
-  if (i == js) {
-    const int ht = tic::CH_HEAD | tic::CH_JOIN | tic::CH_TAIL | (jd.tail2 ? tic::CH_TAIL2 : 0) |
-                   (jd.tail2 && layer_form(h, h->layers[jd.end + 1]) == 1 ? tic::CH_TAIL2_PW : 0);
-    snprintf(buf, sizeof buf, "wino_chain_kernel<0,1,%d,%d>", h->chain_wh, ht);
-  }
-  const int len = (int)strlen(buf);
-  if (len + 1 > cap) return fail(TIC_EINVAL, "name buffer too small (%d < %d)", cap, len + 1);
-  memcpy(name, buf, len + 1);
-  return TIC_OK;
+  const int L = (int)h->layers.size();
+  if (i < 0 || i >= L) return fail(TIC_EINVAL, "layer index %d out of range", i);
+  return name_launch_at(h, plan_launches(h, 0, L, h->tune_reps == 0), i, n, name, cap);
 }
 
 int tic_tuning_export(const tic_handle* h, char* buf, int cap) {
   if (!h || (!buf && cap > 0)) return fail(TIC_EINVAL, "null argument");
-  const tic::ConvEntry* (*regs[3])(int*) = {tic::conv_registry_s1, tic::conv_registry_s2,
-                                           tic::conv_registry_t2};
   std::string t = "tic-tuning 1\n";
   t += "flag fuse01 " + std::to_string((int)h->fuse01) + "\n";
   t += "flag fuse_tail " + std::to_string((int)h->fuse_tail) + "\n";
@@ -2731,7 +2780,7 @@ int tic_tuning_export(const tic_handle* h, char* buf, int cap) {
     const LayerRT& l = h->layers[i];
     for (const auto& kv : l.tuned) {
       int cnt = 0;
-      const tic::ConvEntry* base = regs[kv.second->mode](&cnt);
+      const tic::ConvEntry* base = conv_registry(kv.second->mode, &cnt);
       t += "conv " + std::to_string(i) + " " + std::to_string(kv.first) + " " + std::to_string(kv.second->mode) +
            " " + std::to_string(kv.second - base) + "\n";
     }
@@ -2744,8 +2793,6 @@ int tic_tuning_export(const tic_handle* h, char* buf, int cap) {
 
 int tic_tuning_import(tic_handle* h, const char* text) {
   if (!h || !text) return fail(TIC_EINVAL, "null argument");
-  const tic::ConvEntry* (*regs[3])(int*) = {tic::conv_registry_s1, tic::conv_registry_s2,
-                                           tic::conv_registry_t2};
   const int L = (int)h->layers.size();
   std::vector<std::map<int, const tic::ConvEntry*>> tuned(L);
   std::vector<std::map<int, int>> vars(L);
@@ -2785,32 +2832,22 @@ int tic_tuning_import(tic_handle* h, const char* text) {
       if (sscanf(ln.c_str(), "conv %d %d %d %d", &a, &b, &c, &d) != 4 || a < 0 || a >= L || c < 0 || c > 2)
         return fail(TIC_EINVAL, "tuning line %d: bad conv entry", line);
       int cnt = 0;
-      const tic::ConvEntry* base = regs[c](&cnt);
+      const tic::ConvEntry* base = conv_registry(c, &cnt);
       if (d < 0 || d >= cnt) return fail(TIC_EINVAL, "tuning line %d: registry index %d out of range", line, d);
       const tic::ConvEntry* ce = base + d;
       const LayerDef& ld = h->layers[a].def;
-      const bool last_enc = !h->rmbe() && a == h->n_enc - 1, first_dec = !h->rmbe() && a == h->n_enc;
-      if (ce->mode != ld.kind || ce->cin != ld.cin || ce->cout != ld.cout || ce->act != ld.act ||
-          ce->res != ld.residual || ce->in != (first_dec ? tic::IN_IDX : tic::IN_F32) ||
-          ce->out != (last_enc ? tic::OUT_QUANT : tic::OUT_F32))
+      const ConvSig sig = conv_sig(h, a);
+      if (ce->mode != sig.mode || !sig.matches(*ce))
         return fail(TIC_EINVAL, "tuning line %d: kernel does not match layer %s", line, ld.name.c_str());
       // the form is a policy, never a tuning outcome: the entry's form is its key's
       // (ADVICE r06): entry_form(*ce) must be the form in the key, b >> 24 — or, for a signature
       // that form has no instance of, the form it falls back to (form_fallback), which is what
-      // the tuner itself stores under that key
-      const int hg = ld.kind == K_T2 ? h->layers[a].h_in : h->layers[a].h_out;
+      // the tuner itself stores under that key: the form of the key's candidate list
+      const int hg = sig.hg;
       {
         const int kf = b >> 24;
-        int want = -1;
-        for (int pass = 0; pass < 3 && want < 0 && kf >= 0 && kf <= 2; ++pass) {
-          const int fm = form_fallback(kf, pass);
-          if (fm < 0) break;
-          for (int i = 0; i < cnt && want < 0; ++i)
-            if (base[i].cin == ce->cin && base[i].cout == ce->cout && base[i].act == ce->act && base[i].res == ce->res &&
-                base[i].in == ce->in && base[i].out == ce->out && entry_form(base[i]) == fm && wino4_fits(base[i], hg, hg))
-              want = fm;
-        }
-        if (entry_form(*ce) != want)
+        const auto cands = conv_candidates(sig, kf);
+        if (entry_form(*ce) != (cands.empty() ? -1 : entry_form(*cands[0])))
           return fail(TIC_EINVAL, "tuning line %d: kernel form %d under a form-%d key (layer %s)", line,
                       entry_form(*ce), kf, ld.name.c_str());
       }
@@ -2859,9 +2896,11 @@ int tic_conv3x3_device(tic_handle* h, int kind, int act, const float* d_in, int 
       !b_host)
     return fail(TIC_EINVAL, "bad arguments");
   HIP_TRY(hipSetDevice(h->device));
-  const tic::ConvEntry* e = find_conv(kind, cin, cout, act, d_res ? 1 : 0, tic::IN_F32, tic::OUT_F32,
-                                      kind == K_T2 ? H : out_size(kind, H), kind == K_T2 ? W : out_size(kind, W), n,
-                                      kind == K_S1 ? h->s1_form : h->s2_form);
+  // (a caller's own shape, not a layer of the handle: the one signature built outside conv_sig)
+  const ConvSig sig{kind,        cin,          cout, act, d_res ? 1 : 0,
+                    tic::IN_F32, tic::OUT_F32, kind == K_T2 ? H : out_size(kind, H)};
+  const tic::ConvEntry* e =
+      find_conv(sig, n, kind == K_S1 ? h->s1_form : h->s2_form, kind == K_T2 ? W : out_size(kind, W));
   if (!e)
     return fail(TIC_EUNSUPPORTED, "no compiled conv3x3 for kind %d %d->%d act %d res %d", kind, cin, cout, act,
                 d_res ? 1 : 0);
