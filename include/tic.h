@@ -105,7 +105,17 @@ int tic_rmbe_device(tic_handle* h, const float* d_windows, int n, float* d_out);
  * patches per launch sequence, default 256, env TIC_MAX_CHUNK), "graph" (1: replay
  * tic_codec_device as a captured HIP graph per (buffers, n) — default 0: measured slower
  * than eager dual-lane launches on MI355X), "persist_grid" (> 0: cap on the grid of the
- * persistent conv variants, so that tests run several tiles per workgroup; default 0).
+ * persistent conv variants, so that tests run several tiles per workgroup; default 0),
+ * "poison" (test hook, default 0; 1: every pass of the layer runner — behind tic_encode[_device],
+ * tic_decode[_device], tic_codec_device, tic_rmbe[_device] and tic_rmbe_image_device — first fills,
+ * on its lane's own stream, the lane's three activation workspaces, the lane's chain hand-off
+ * buffer and the slices of the handle's own output staging (host entries, whole-image windows) it
+ * is about to write with the 32-bit word 0x7FC5A5A5: a NaN as float, the bytes 165, 165, 197, 127
+ * as symbols or pixels.  A kernel that leaves an element unwritten, or reads a hand-off before it
+ * is published, then no longer finds the previous run's value there.  The hand-off flags and
+ * control words, timing-probe buffers, weights, tables, input staging and every caller-owned
+ * buffer are left alone; tic_autotune, tic_autotune_step and tic_profile_layers run without the
+ * fills.  "poison" 1 and "graph" 1 exclude each other: whichever is set second is TIC_EINVAL).
  * Structural, bit-identical fusions (1 on, 0 off, -1 the model's default): "fuse01"
  * (encode_0 + encode_1 in one launch; default on), "fuse_tail" (decode_1 + decode_0; on),
  * "chain" (each run of stride-1 64->64 layers in one launch; on for models 0-2, off for

@@ -159,15 +159,43 @@ UNCLIPPED_GAIN = {0: 1 / 8, 1: 1 / 4, 2: 1 / 8, 3: 1 / 32, 128: 1 / 32}
 UNCLIPPED_CASES = [(0, 64), (1, 32), (2, 32), (3, 64), (128, 64)]
 
 
-def unclipped_params(model_id, seed=0):
+def unclipped_params(model_id, seed=0, gain=None):
     """synthetic params with the last decoder layer's kernel scaled by UNCLIPPED_GAIN (bias
-    unchanged): with the plain synthetic weights up to 85 % of the oracle's outputs are exactly 0
-    or 255 and the float and byte bars see nothing of the last layers there."""
+    unchanged; `gain`: a case's own value instead): with the plain synthetic weights up to 85 % of
+    the oracle's outputs are exactly 0 or 255 and the float and byte bars see nothing of the last
+    layers there."""
     from tf_image_compression_amd.weights import synthetic_params
     params = dict(synthetic_params(model_id, seed=seed))
     name = last_decoder_layer(model_id)
-    params[f"{name}/kernel"] = (params[f"{name}/kernel"] * np.float32(UNCLIPPED_GAIN[model_id])).astype(np.float32)
+    gain = UNCLIPPED_GAIN[model_id] if gain is None else gain
+    params[f"{name}/kernel"] = (params[f"{name}/kernel"] * np.float32(gain)).astype(np.float32)
     return params
+
+
+# ---------------------------------------------------------------------------
+# The geometry sweep (test_gpu_geometry.py; input conditions: test_parity_inputs_host.py).
+# (model, P): the chain's 8x8 regions at stage sides the other modules never compare with
+# anything — model_0/1 stage P/16: 1, 2, 5, 7 (one partial region, odd Winograd half tiles), 8
+# (exactly one full region), 9 = 8 + 1 (a 1-wide partial region whose only column is its hand-off
+# column), 10 = 8 + 2, 15, 17 = 8 + 8 + 1; model_2 stage P/8 (2, 6, 10, 18) with the stride-2
+# quantiser layer behind it; model_3 stages P/4 and P/8 (4/2, 12/6, 20/10, 36/18); ch_128 stage
+# P/4 at the odd sides 5, 7, 9 of its 128-wide Winograd, transposed and stride-2 instances.
+# ---------------------------------------------------------------------------
+GEOMETRY_CASES = ([(0, P) for P in (16, 32, 80, 112, 128, 144, 160, 240, 272)] + [(1, 16), (1, 144)] +
+                  [(2, P) for P in (16, 48, 80, 144)] + [(3, P) for P in (16, 48, 80, 144)] +
+                  [(128, P) for P in (20, 28, 36)])
+GEOMETRY_N = 3  # two lanes get 2 + 1 patches
+# model_1 at P = 144 with the module's gain of 1/4: 1.9e-2 of the oracle's outputs are exactly 0 or 255
+GEOMETRY_UNCLIPPED_GAIN = {(1, 144): 1 / 8}
+
+
+def geometry_patches(model_id, P):
+    from tf_image_compression_amd.synthetic import structured_patches
+    return structured_patches(GEOMETRY_N, P, seed=1000 + model_id + P)
+
+
+def geometry_unclipped_params(model_id, P):
+    return unclipped_params(model_id, gain=GEOMETRY_UNCLIPPED_GAIN.get((model_id, P)))
 
 
 def clipped_share_and_span(ref_f):
@@ -247,6 +275,18 @@ def set_options(codec, **kw):
     opts.update(kw)
     for k, v in opts.items():
         codec.set_option(k, v)
+
+
+POISON_WORD = 0x7FC5A5A5  # tic.h, option "poison": a NaN as f32; bytes 165, 165, 197, 127
+
+
+def poisoned(codec):
+    """Turn option "poison" on for a handle and return it: from here on every pass starts from
+    workspaces, hand-off buffer and output staging that hold POISON_WORD, so a bit-identity check
+    on one handle no longer finds the previous run's (equal, hence right) values in what a kernel
+    left unwritten.  Not for handles whose test measures time, tunes or replays a graph."""
+    codec.set_option("poison", 1)
+    return codec
 
 
 def layer_index(codec, name):

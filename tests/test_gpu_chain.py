@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from conftest import structured_patches
+from gpu_checks import poisoned
 
 pytestmark = pytest.mark.gpu
 
@@ -20,7 +21,7 @@ pytestmark = pytest.mark.gpu
 def _codec(model_id, P):
     from tf_image_compression_amd.codec import Codec
     from tf_image_compression_amd.weights import synthetic_params, SYNTH_MEAN, SYNTH_STD
-    return Codec(model_id, synthetic_params(model_id, seed=0), SYNTH_MEAN, SYNTH_STD, patch_size=P)
+    return poisoned(Codec(model_id, synthetic_params(model_id, seed=0), SYNTH_MEAN, SYNTH_STD, patch_size=P))
 
 
 def _run(c, x):

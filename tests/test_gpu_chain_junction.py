@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 from conftest import structured_patches
+from gpu_checks import poisoned
 
 pytestmark = pytest.mark.gpu
 
@@ -24,7 +25,8 @@ JOINED = re.compile(r"wino_chain_kernel<0,1,2,(\d+)>")
 def _codec(model_id, P, Q=2):
     from tf_image_compression_amd.codec import Codec
     from tf_image_compression_amd.weights import synthetic_params, SYNTH_MEAN, SYNTH_STD
-    return Codec(model_id, synthetic_params(model_id, seed=0), SYNTH_MEAN, SYNTH_STD, patch_size=P, quan_scale=Q)
+    return poisoned(Codec(model_id, synthetic_params(model_id, seed=0), SYNTH_MEAN, SYNTH_STD, patch_size=P,
+                          quan_scale=Q))
 
 
 class _Bufs:
@@ -252,6 +254,7 @@ def test_joined_launch_graph_replay():
         assert _joined_ht(c, n // 2) is not None
         b = _Bufs(c, structured_patches(n, P, seed=980))
         ref = b.codec()
+        c.set_option("poison", 0)  # graph replay runs unpoisoned: the two options exclude each other
         c.set_option("graph", 1)
         for _ in range(3):  # capture, then replays
             got = b.codec()

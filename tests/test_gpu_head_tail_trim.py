@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 from conftest import structured_patches
+from gpu_checks import poisoned
 
 pytestmark = pytest.mark.gpu
 
@@ -31,7 +32,7 @@ def lib_codec():
 
     def get(model_id, P):
         if (model_id, P) not in cache:
-            c = Codec(model_id, synthetic_params(model_id, seed=0), SYNTH_MEAN, SYNTH_STD, patch_size=P)
+            c = poisoned(Codec(model_id, synthetic_params(model_id, seed=0), SYNTH_MEAN, SYNTH_STD, patch_size=P))
             c.set_option("streams", 2)
             cache[model_id, P] = c
         return cache[model_id, P]
@@ -97,7 +98,7 @@ def _check_byte_rounding(model_id, last, bias, want, P, kernel):
     params = dict(synthetic_params(model_id, seed=0))
     params[f"{last}/kernel"] = np.zeros_like(params[f"{last}/kernel"])
     params[f"{last}/bias"] = np.asarray(bias, np.float32)
-    with Codec(model_id, params, [0.5, 0.5, 0.5], [1.0, 1.0, 1.0], patch_size=P) as c:
+    with poisoned(Codec(model_id, params, [0.5, 0.5, 0.5], [1.0, 1.0, 1.0], patch_size=P)) as c:
         assert c.layers()[-1][0] == last
         idx = c.encode(structured_patches(3, P, seed=7))
         try:

@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 from conftest import structured_patches
-from gpu_checks import check_codec as _check_codec, codec_mean, codec_std  # noqa: F401
+from gpu_checks import check_codec as _check_codec, codec_mean, codec_std, poisoned  # noqa: F401
 from oracle import tic_oracle as o
 
 pytestmark = pytest.mark.gpu
@@ -30,7 +30,8 @@ def lib_codec():
         key = (model_id, P, Q)
         if key not in cache:
             params = synthetic_params(model_id, seed=0)
-            cache[key] = (Codec(model_id, params, SYNTH_MEAN, SYNTH_STD, patch_size=P, quan_scale=Q), params)
+            c = Codec(model_id, params, SYNTH_MEAN, SYNTH_STD, patch_size=P, quan_scale=Q)
+            cache[key] = (poisoned(c), params)
         return cache[key]
 
     yield get
@@ -326,7 +327,7 @@ def test_fused_rmbe_first_layers_bit_identical(monkeypatch):
     from tf_image_compression_amd.topology import RMBE_ID
     r = np.random.default_rng(4)
     win = np.clip(r.normal(120, 50, (3, 128, 128, 3)), 0, 255).astype(np.float32)
-    with Codec(RMBE_ID, synthetic_params(RMBE_ID), SYNTH_MEAN, SYNTH_STD, patch_size=128) as c:
+    with poisoned(Codec(RMBE_ID, synthetic_params(RMBE_ID), SYNTH_MEAN, SYNTH_STD, patch_size=128)) as c:
         c.set_option("fuse01", 0)
         a = c.rmbe_windows(win)
         c.set_option("fuse01", 1)
@@ -350,7 +351,7 @@ def test_rmbe_network(lib_codec):
     params = synthetic_params(RMBE_ID)
     r = np.random.default_rng(3)
     win = np.clip(r.normal(120, 50, (3, 128, 128, 3)), 0, 255).astype(np.float32)
-    with Codec(RMBE_ID, params, SYNTH_MEAN, SYNTH_STD, patch_size=128) as c:
+    with poisoned(Codec(RMBE_ID, params, SYNTH_MEAN, SYNTH_STD, patch_size=128)) as c:
         got = c.rmbe_windows(win)
     ref = o.rmbe_model(params, SYNTH_MEAN, SYNTH_STD, win)
     assert float(np.max(np.abs(got - ref))) <= 2e-3
@@ -366,7 +367,7 @@ def test_codec_vs_golden_fixture(name):
     from tf_image_compression_amd.weights import synthetic_params
     z = np.load(os.path.join(GOLDEN, name), allow_pickle=False)
     m, P = int(z["model_id"]), int(z["patch"])
-    with Codec(m, synthetic_params(m, seed=0), z["mean"], z["std"], patch_size=P) as c:
+    with poisoned(Codec(m, synthetic_params(m, seed=0), z["mean"], z["std"], patch_size=P)) as c:
         idx, pre = c.encode(z["patches"], return_preact=True)
         rgb = c.decode(z["idx"])
     ref = z["preact"]
@@ -421,7 +422,7 @@ def test_fused_tail_rmbe_bit_identical():
     from tf_image_compression_amd.topology import RMBE_ID
     r = np.random.default_rng(5)
     win = np.clip(r.normal(120, 50, (3, 128, 128, 3)), 0, 255).astype(np.float32)
-    with Codec(RMBE_ID, synthetic_params(RMBE_ID), SYNTH_MEAN, SYNTH_STD, patch_size=128) as c:
+    with poisoned(Codec(RMBE_ID, synthetic_params(RMBE_ID), SYNTH_MEAN, SYNTH_STD, patch_size=128)) as c:
         c.set_option("fuse_tail", 0)
         a = c.rmbe_windows(win)
         c.set_option("fuse_tail", 1)

@@ -17,7 +17,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, structured_patches
-from gpu_checks import check_codec_subset
+from gpu_checks import check_codec_subset, poisoned
 from oracle import tic_oracle as o
 
 pytestmark = pytest.mark.gpu
@@ -35,7 +35,7 @@ def _plain_codec(model_id, params, P):
     c = Codec(model_id, params, SYNTH_MEAN, SYNTH_STD, patch_size=P, tuning="none")
     for k in ("fuse01", "fuse_tail", "chain"):
         c.set_option(k, 0)
-    return c
+    return poisoned(c)
 
 
 @pytest.fixture
@@ -81,7 +81,7 @@ def test_tuned_model0_p256_batch64_vs_oracle_and_plain(m0_module):
     """configs[1] exactly as timed (batch 64, two lanes of 32, shipped tuning): oracle on
     four patches, and every symbol / byte of all 64 equal to the unfused default path."""
     mod, params = m0_module
-    c = mod.codec(256, 2)
+    c = poisoned(mod.codec(256, 2))
     x = np.concatenate([structured_patches(4, 256, seed=1101),
                         np.random.default_rng(1102).integers(0, 256, (60, 256, 256, 3), dtype=np.uint8)])
     idx, rgb = check_codec_subset(c, params, 0, 256, x, k=4)
@@ -120,7 +120,7 @@ def test_tuned_model3_p256_batch256_vs_oracle_and_plain():
     from tf_image_compression_amd.codec import Codec
     from tf_image_compression_amd.weights import synthetic_params, SYNTH_MEAN, SYNTH_STD
     params = synthetic_params(3, seed=0)
-    with Codec(3, params, SYNTH_MEAN, SYNTH_STD, patch_size=256) as c:
+    with poisoned(Codec(3, params, SYNTH_MEAN, SYNTH_STD, patch_size=256)) as c:
         assert c.tuning_source.startswith("shipped tuning:"), c.tuning_source
         k = _kernels_of(c, 128)
         assert "enc01_kernel" in k and "dec10_kernel" in k, k

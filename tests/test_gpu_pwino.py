@@ -16,7 +16,7 @@ import numpy as np
 import pytest
 
 from conftest import structured_patches
-from gpu_checks import check_codec as _check_codec
+from gpu_checks import check_codec as _check_codec, poisoned
 from oracle import tic_oracle as o
 
 pytestmark = pytest.mark.gpu
@@ -40,7 +40,7 @@ SIZES = [(32, 32), (17, 15), (5, 9), (70, 66), (1, 3)]
 def codec():
     from tf_image_compression_amd.codec import Codec
     from tf_image_compression_amd.weights import synthetic_params, SYNTH_MEAN, SYNTH_STD
-    c = Codec(0, synthetic_params(0, seed=0), SYNTH_MEAN, SYNTH_STD, patch_size=64)
+    c = poisoned(Codec(0, synthetic_params(0, seed=0), SYNTH_MEAN, SYNTH_STD, patch_size=64))
     yield c
     c.close()
 
@@ -81,7 +81,7 @@ def test_codec_s2_form_parity(model_id, P):
     from tf_image_compression_amd.codec import Codec
     from tf_image_compression_amd.weights import synthetic_params, SYNTH_MEAN, SYNTH_STD
     params = synthetic_params(model_id, seed=0)
-    with Codec(model_id, params, SYNTH_MEAN, SYNTH_STD, patch_size=P) as c:
+    with poisoned(Codec(model_id, params, SYNTH_MEAN, SYNTH_STD, patch_size=P)) as c:
         patches = structured_patches(3, P, seed=910 + model_id + P)
         c.set_option("s2_form", 1)
         kern = c.layer_kernels(len(patches))
@@ -93,7 +93,7 @@ def test_codec_s2_form_parity(model_id, P):
 def test_s2_form_independent_of_fusions(model_id, P, n):
     from tf_image_compression_amd.codec import Codec
     from tf_image_compression_amd.weights import synthetic_params, SYNTH_MEAN, SYNTH_STD
-    with Codec(model_id, synthetic_params(model_id, seed=0), SYNTH_MEAN, SYNTH_STD, patch_size=P) as c:
+    with poisoned(Codec(model_id, synthetic_params(model_id, seed=0), SYNTH_MEAN, SYNTH_STD, patch_size=P)) as c:
         x = structured_patches(n, P, seed=930 + model_id)
         c.set_option("s2_form", 1)
 
@@ -129,7 +129,7 @@ def test_chain_decode2_pwino_bit_identical(model_id, P, n):
     with partial ones (P = 288), one and two lanes.  Reference: model_0/model.py:198-222."""
     from tf_image_compression_amd.codec import Codec
     from tf_image_compression_amd.weights import synthetic_params, SYNTH_MEAN, SYNTH_STD
-    with Codec(model_id, synthetic_params(model_id, seed=0), SYNTH_MEAN, SYNTH_STD, patch_size=P) as c:
+    with poisoned(Codec(model_id, synthetic_params(model_id, seed=0), SYNTH_MEAN, SYNTH_STD, patch_size=P)) as c:
         x = structured_patches(n, P, seed=950 + model_id + P)
         c.set_option("s1_form", 1)
         c.set_option("s2_form", 1)

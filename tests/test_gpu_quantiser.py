@@ -44,7 +44,8 @@ def handles():
         key = (model_id, P, Q, tag)
         if key not in cache:
             params = make_params()
-            cache[key] = (Codec(model_id, params, g.codec_mean(), g.codec_std(), patch_size=P, quan_scale=Q), params)
+            c = Codec(model_id, params, g.codec_mean(), g.codec_std(), patch_size=P, quan_scale=Q)
+            cache[key] = (g.poisoned(c), params)
         return cache[key]
 
     yield get

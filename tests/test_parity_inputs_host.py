@@ -1,7 +1,8 @@
 """The input conditions the GPU tests of the quantiser, the dequantiser and the unclipped
 decoder rely on (test_gpu_quantiser.py, test_gpu_dequantiser.py), asserted on the CPU with the
 oracle alone: a later change of synthetic_params or structured_patches must not silently empty
-those tests.  Reference: the quantiser round(sigmoid(x) * (Q-1)) of model_0/model.py:136-138
+those tests; likewise for the geometry sweep (test_gpu_geometry.py), for exactly its patches.
+Reference: the quantiser round(sigmoid(x) * (Q-1)) of model_0/model.py:136-138
 (tf.round: half to even), the dequantiser :148-155, denormalise + clip :250-259."""
 import numpy as np
 import pytest
@@ -64,3 +65,23 @@ def test_unclipped_params_leave_nothing_clipped(model_id, P):
     ref_f, _ = o.decoder(params, g.codec_mean(), g.codec_std(), idx, 2, model_id)
     share, span = g.clipped_share_and_span(ref_f)
     assert share <= 0.01 and span >= 100, (share, span)
+
+
+@pytest.mark.parametrize("model_id,P", g.GEOMETRY_CASES)
+def test_geometry_sweep_inputs(model_id, P):
+    """test_gpu_geometry.py's patches: at most 1e-3 of the symbols inside check_codec's 1e-5
+    decision band (the symbol bar says nothing there), and on the unclipped parameters at most 1e-3
+    of the oracle's reconstruction exactly 0 or 255 (the float and byte bars see no last layer
+    there)."""
+    x = g.geometry_patches(model_id, P)
+    assert x.shape == (g.GEOMETRY_N, P, P, 3)
+    from tf_image_compression_amd.weights import synthetic_params
+    pre, idx = o.encoder(synthetic_params(model_id, seed=0), g.codec_mean(), g.codec_std(), x, P, 2, model_id)
+    scale = max(1.0, float(np.max(np.abs(pre))))
+    band = float(np.mean(o.decision_margin(pre, 2) <= 1e-5 * scale))
+    params = g.geometry_unclipped_params(model_id, P)
+    ref_f, _ = o.decoder(params, g.codec_mean(), g.codec_std(), idx, 2, model_id)
+    share, span = g.clipped_share_and_span(ref_f)
+    print(f"\ngeometry model {model_id} P {P}: band share {band:.2e} clipped share {share:.2e} span {span:.1f}")
+    assert band <= 1e-3, band
+    assert share <= 1e-3, share

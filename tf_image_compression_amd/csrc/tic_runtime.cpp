@@ -503,6 +503,8 @@ struct tic_handle {
   bool fuse01 = false;  // encode_0 -> encode_1 through LDS (enc01_kernel); default: struct_defaults
   int persist_grid = 0;  // cap on persistent-kernel grids (0: CUs x resident workgroups); tests
   int wino4_max_n = 0;   // > 0: F(4x4,3x3) launches split into this many patches (tests of the split path)
+  bool poison = false;   // option "poison" (tests): every pass fills its scratch first (poison_pass)
+  int poison_hold = 0;   // > 0 inside the tuning / profiling entries: no fills there
   int s1_form = 0;       // stride-1 layers: 0 direct implicit GEMM, 1 Winograd F(2x2,3x3), 2 F(4x4,3x3)
   int s2_form = 0;       // standalone stride-2 / transposed layers: 0 direct, 1 polyphase Winograd
                          // (layers a fused kernel could run keep the direct form: pwino_layer)
@@ -571,6 +573,11 @@ static const float* conv_weights(const LayerRT& l, const tic::ConvEntry* e) {
 
 namespace {
 
+// Option "poison": the word scratch is filled with.  A NaN as f32; its bytes (165, 165, 197,
+// 127) are none of 0, 1, 255, the values a symbol or a clipped pixel most often holds, and as a
+// symbol each stays inside the dequantiser's 256-entry table.
+constexpr unsigned kPoisonWord = 0x7FC5A5A5u;
+
 int ensure(void** p, size_t* have, size_t need) {
   if (*have >= need) return TIC_OK;
   if (*p) (void)hipFree(*p);
@@ -619,6 +626,9 @@ int ensure_chain(tic_handle* h, Lane& ln, int nl, int n, int R) {
     ln.xbuf_floats = 0;
     HIP_TRY(hipMalloc((void**)&ln.xbuf, std::max<size_t>(xf, 64) * sizeof(float)));
     ln.xbuf_floats = xf;
+    // grown inside a pass, behind poison_pass: a fresh buffer starts poisoned too
+    if (h->poison && h->poison_hold == 0)
+      HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)ln.xbuf, (int)kPoisonWord, std::max<size_t>(xf, 64), ln.stream));
   }
   if (ln.cflags_n < nf) {
     clear_graphs(h);
@@ -628,6 +638,32 @@ int ensure_chain(tic_handle* h, Lane& ln, int nl, int n, int R) {
     HIP_TRY(hipMalloc((void**)&ln.cflags, std::max<size_t>(nf, 16) * sizeof(unsigned)));
     HIP_TRY(hipMemsetAsync(ln.cflags, 0, std::max<size_t>(nf, 16) * sizeof(unsigned), ln.stream));
     ln.cflags_n = nf;
+  }
+  return TIC_OK;
+}
+
+// Fill [p, p + bytes) with kPoisonWord as laid out from `base` (4-byte aligned): whole words by a
+// 32-bit fill, the at most three bytes at either ragged end one by one, so that neighbouring
+// lanes' slices of one buffer never touch each other's bytes.
+int poison_fill(const void* base, void* p, size_t bytes, hipStream_t st) {
+  uintptr_t lo = (uintptr_t)p, hi = lo + bytes;
+  const uintptr_t b0 = (uintptr_t)base;
+  auto byte_at = [&](uintptr_t a) { return (int)(kPoisonWord >> (8 * ((a - b0) & 3)) & 0xff); };
+  for (; lo < hi && ((lo - b0) & 3); ++lo) HIP_TRY(hipMemsetAsync((void*)lo, byte_at(lo), 1, st));
+  for (; hi > lo && ((hi - b0) & 3); --hi) HIP_TRY(hipMemsetAsync((void*)(hi - 1), byte_at(hi - 1), 1, st));
+  if (hi > lo) HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)lo, (int)kPoisonWord, (hi - lo) / 4, st));
+  return TIC_OK;
+}
+
+// The part of a pass's output [p, p + bytes) that lies in one of the handle's own staging
+// buffers (st_out, st_out2, win_out): a caller's buffer is the caller's to fill.
+int poison_staging(const tic_handle* h, void* p, size_t bytes, hipStream_t st) {
+  if (!p) return TIC_OK;
+  const std::pair<void*, size_t> own[3] = {
+      {h->st_out, h->st_out_bytes}, {h->st_out2, h->st_out2_bytes}, {h->win_out, h->win_out_bytes}};
+  for (const auto& o : own) {
+    const uintptr_t b = (uintptr_t)o.first, a = (uintptr_t)p;
+    if (o.first && a >= b && a + bytes <= b + o.second) return poison_fill(o.first, p, bytes, st);
   }
   return TIC_OK;
 }
@@ -1435,6 +1471,29 @@ static int enqueue_conv(const Pass& ps, const Rot& r, int li) {
   return TIC_OK;
 }
 
+// Option "poison" (a test hook): before a pass's first launch, on the lane's own stream, fill
+// everything the pass may find an earlier run's values in: the lane's three workspaces, its chain
+// hand-off buffer, and the slices of the handle's host-entry / whole-image staging the pass is
+// about to write.  A kernel that leaves an element unwritten, or reads a hand-off before it is
+// published, then yields NaN or a wrong byte where it would have found the previous (identical)
+// run's correct value.  Not touched: cflags / ctl (the epoch protocol lives on their old
+// values; a changed flag could hang a launch), the tstamp buffers (probes), weights and tables,
+// st_in / win_in (the pass's input) and whatever the caller owns.
+int poison_pass(tic_handle* h, Lane& ln, int n, uint8_t* d_idx, float* d_pre, uint8_t* d_rgb, float* d_f32) {
+  hipStream_t const st = ln.stream;
+  for (float* b : ln.ws)
+    if (b) HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)b, (int)kPoisonWord, h->act_elems * (size_t)ln.ws_batch, st));
+  if (ln.xbuf)
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)ln.xbuf, (int)kPoisonWord, std::max<size_t>(ln.xbuf_floats, 64), st));
+  const LayerRT& lq = h->layers[std::max(h->n_enc, 1) - 1];  // the quantiser layer: the code's shape
+  const size_t ce = h->rmbe() ? 0 : (size_t)n * lq.h_out * lq.h_out * lq.def.cout, px = (size_t)n * h->P * h->P * 3;
+  int rc = poison_staging(h, d_idx, ce, st);
+  if (!rc) rc = poison_staging(h, d_pre, ce * 4, st);
+  if (!rc) rc = poison_staging(h, d_rgb, px, st);
+  if (!rc) rc = poison_staging(h, d_f32, px * 4, st);
+  return rc;
+}
+
 // Run layers [l0, l1) for n patches: the launches plan_launches gives, in order.  A pass over
 // both halves of a codec ([0, L): tic_codec_device) reads the decoder's symbols from d_idx, and
 // runs the encoder's last and the decoder's first chain launch as one where the plan joins them.
@@ -1445,6 +1504,9 @@ int run_layers(tic_handle* h, Lane& ln, int l0, int l1, const void* in, int n, u
   Pass ps{h, ln, in, !h->rmbe() && l0 < h->n_enc && l1 > h->n_enc ? (const void*)d_idx : in, n, d_idx, d_pre, d_rgb,
           d_f32, 0};
   if (const char* s = getenv("TIC_PROBE_SKIP")) ps.probe_skip = strtoull(s, nullptr, 0);
+  if (h->poison && h->poison_hold == 0) {
+    if (int rc = poison_pass(h, ln, n, d_idx, d_pre, d_rgb, d_f32)) return rc;
+  }
   Rot r;
   int marked = -1;  // event pair open around the launch of layer mark_layer
   auto mark_close = [&]() -> int {
@@ -2176,7 +2238,15 @@ int tic_set_option(tic_handle* h, const char* key, int value) {
     return TIC_OK;
   }
   if (k == "graph") {
+    if (value != 0 && h->poison) return fail(TIC_EINVAL, "graph cannot be combined with poison");
     h->use_graph = value != 0;
+    return TIC_OK;
+  }
+  if (k == "poison") {  // tests: fill scratch before every pass (poison_pass); not under graph replay
+    if (value < 0 || value > 1) return fail(TIC_EINVAL, "poison must be 0 or 1");
+    if (value != 0 && h->use_graph) return fail(TIC_EINVAL, "poison cannot be combined with graph");
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->poison = value != 0;
     return TIC_OK;
   }
   if (k == "fuse_tail") {
@@ -2327,9 +2397,19 @@ int tic_layer_info(const tic_handle* h, int i, char* name_buf, int name_len, int
   return fill_layer_info(h->layers[i].def, name_buf, name_len, kind, cin, cout, act, stage, residual);
 }
 
+// Timing and tuning entries measure the launches alone: option "poison" is off inside them.
+namespace {
+struct PoisonHold {
+  tic_handle* h;
+  explicit PoisonHold(tic_handle* hh) : h(hh) { ++h->poison_hold; }
+  ~PoisonHold() { --h->poison_hold; }
+};
+}  // namespace
+
 int tic_profile_layers(tic_handle* h, const void* d_in, int n, int iters, float* ms_out) {
   int rc = check_ready(h);
   if (rc) return rc;
+  PoisonHold hold(h);
   if (!d_in || n <= 0 || iters <= 0 || !ms_out) return fail(TIC_EINVAL, "bad arguments");
   if (n > h->chunk) return fail(TIC_EINVAL, "profile n %d exceeds chunk %d", n, h->chunk);
   const int L = (int)h->layers.size();
@@ -2361,6 +2441,7 @@ int tic_profile_layers(tic_handle* h, const void* d_in, int n, int iters, float*
 int tic_autotune(tic_handle* h, const void* d_in, int n, int reps) {
   int rc = check_ready(h);
   if (rc) return rc;
+  PoisonHold hold(h);
   if (!d_in || n <= 0 || reps <= 0) return fail(TIC_EINVAL, "bad arguments");
   if (n > h->chunk) return fail(TIC_EINVAL, "autotune n %d exceeds chunk %d", n, h->chunk);
   for (auto& l : h->layers) {
@@ -2388,6 +2469,7 @@ int tic_autotune(tic_handle* h, const void* d_in, int n, int reps) {
 int tic_autotune_step(tic_handle* h, const void* d_in, int n, int rounds, int reps) {
   int rc = check_ready(h);
   if (rc) return rc;
+  PoisonHold hold(h);
   if (!d_in || n <= 0 || rounds <= 0 || reps <= 0) return fail(TIC_EINVAL, "bad arguments");
   if (n > h->chunk) return fail(TIC_EINVAL, "autotune_step n %d exceeds chunk %d", n, h->chunk);
   // per-launch batch sizes the lanes will see for n
