@@ -267,6 +267,129 @@ def wino4_float_bar(err_direct):
     return min(2.0 * max(float(err_direct), 1e-3), 1e-2)
 
 
+# ---------------------------------------------------------------------------
+# The rmbe post-filter: the window network and the whole-image driver (test_gpu_rmbe.py,
+# test_gpu_product.py; input conditions: test_parity_inputs_host.py).  Nothing below needs a GPU.
+# Reference: submit/2/rmbe/model.py:113-197 (the net), submit/2/rmbe/rmbe.py:15-111 (the passes).
+# ---------------------------------------------------------------------------
+# the variant tables of the fused head, the fused tail and the VALU last layer (conv_rgb.hip
+# enc01_variants(): TH1 2/4 padded, 2/4/8 compact; dec10_variants(): PK x PF x TA x CMP;
+# convT_rgb_valu.h: TW 64/32/16 one-shot, then persistent)
+ENC01_VARIANTS = range(5)
+DEC10_VARIANTS = range(16)
+RGB_OUT_TILES = range(6)
+RGB_OUT_PERSISTENT_FROM = 3
+
+RMBE_P, RMBE_OFF = 128, 64
+# (H, W): ((hn, wn) of pass 1, (hn, wn) of pass 2) — 0 windows where either count is 0
+RMBE_IMAGES = {
+    (128, 192): ((1, 1), (0, 1)),   # pass 1 is 1 x 1, pass 2 has no window
+    (192, 128): ((1, 0), (1, 1)),   # pass 1 has no window, pass 2 is 1 x 1
+    (192, 192): ((1, 1), (1, 1)),   # one window each, overlapping
+    (191, 191): ((1, 0), (0, 1)),   # no window in either pass
+    (200, 330): ((1, 2), (1, 2)),
+    (320, 448): ((2, 3), (2, 3)),   # hn != wn; at chunk 4: 4 + 2 windows, 2 + 2 and 1 + 1 per lane
+    (448, 320): ((3, 2), (3, 2)),
+}
+
+
+RMBE_NET_FLOAT = slice(0, 4)    # rmbe_net_windows(): the windows whose oracle output clips nowhere
+RMBE_NET_FLAT255 = slice(4, 5)  # the all-255 window: 12.6 % of its oracle output is exactly 0
+RMBE_4K_PASSES = (464, 480)     # windows per pass of 3840 x 2160: 16 x 29 and 16 x 30
+
+
+def rmbe_pass_checked(n):
+    """The windows of a pass-sized call compared with the oracle: the first two (the first chunk's
+    first lane), the first of the second chunk (its first lane) and the last two (its last lane)."""
+    return [0, 1, 256, n - 2, n - 1]
+
+
+def rmbe_params():
+    from tf_image_compression_amd.topology import RMBE_ID
+    from tf_image_compression_amd.weights import synthetic_params
+    return synthetic_params(RMBE_ID, seed=0)
+
+
+def structured_image(H, W, seed):
+    """The smooth-plus-noise uint8 image of the whole-image tests (test_gpu_image.py's _image)."""
+    r = np.random.default_rng(seed)
+    yy, xx = np.mgrid[0:H, 0:W]
+    base = 128 + 60 * np.sin(xx / 17.0)[..., None] * np.cos(yy / 23.0)[..., None] + r.normal(0, 12, (H, W, 3))
+    return np.clip(base, 0, 255).astype(np.uint8)
+
+
+def rmbe_image(H, W):
+    """The float32 image of a whole-image case ((200, 330): test_rmbe_whole_image's seed)."""
+    return structured_image(H, W, 11 if (H, W) == (200, 330) else 7 * H + W).astype(np.float32)
+
+
+def rmbe_window_counts(H, W):
+    """((hn, wn), (hn, wn)) of the two passes (rmbe.py:70-72 and :92-94)."""
+    return ((H // RMBE_P, (W - RMBE_OFF) // RMBE_P), ((H - RMBE_OFF) // RMBE_P, W // RMBE_P))
+
+
+def rmbe_net_windows():
+    """Five windows: two crops of a structured image, one of clipped Gaussian noise
+    (test_rmbe_network's), all 0 and all 255 — the flat ones show the SAME padding and the f32
+    normalise at the border, where a padded tap must read 0.0 and not (0 - mean) / std."""
+    img = structured_image(300, 400, 3).astype(np.float32)
+    w = np.empty((5, RMBE_P, RMBE_P, 3), np.float32)
+    w[0] = img[:128, :128]
+    w[1] = img[150:278, 201:329]
+    w[2] = np.clip(np.random.default_rng(3).normal(120, 50, (RMBE_P, RMBE_P, 3)), 0, 255)
+    w[3] = 0
+    w[4] = 255
+    return w
+
+
+def rmbe_pass_windows(n):
+    """n windows as the 4K image's passes bring them: clipped Gaussian noise, with crops of a
+    structured image at 0, 255, 256 (the two sides of the handle's chunk boundary) and n - 1."""
+    r = np.random.default_rng(464)
+    w = np.clip(r.normal(120, 50, (n, RMBE_P, RMBE_P, 3)), 0, 255).astype(np.float32)
+    img = structured_image(256, 256, 5).astype(np.float32)
+    for k, (y, x) in zip((0, 255, 256, n - 1), ((0, 0), (0, 128), (128, 0), (128, 128))):
+        w[k] = img[y:y + RMBE_P, x:x + RMBE_P]
+    return w
+
+
+def rmbe_reference(params, windows):
+    """(ref, E32): the f64-accumulated oracle of the window network, and the max distance of the
+    same oracle accumulated in f32 from it over this call (decoder_reference's rule)."""
+    ref = o.rmbe_model(params, codec_mean(), codec_std(), windows)
+    f32 = o.rmbe_model(params, codec_mean(), codec_std(), windows, acc=np.float32)
+    return ref, float(np.max(np.abs(f32.astype(np.float64) - ref)))
+
+
+def rmbe_image_reference(params, img):
+    """(ref, E32) of the two-pass whole-image filter, as rmbe_reference (E32 over both passes;
+    0.0 for an image without a window, whose reference is the image itself)."""
+    ref = o.rmbe(img, params, codec_mean(), codec_std())
+    f32 = o.rmbe(img, params, codec_mean(), codec_std(), acc=np.float32)
+    return ref, float(np.max(np.abs(f32.astype(np.float64) - ref)))
+
+
+def rmbe_clipped_share(ref, changed=None):
+    """Share of oracle outputs exactly 0 or 255 among the values the filter changes (all of a
+    window batch; of an image, the pixels inside a window of either pass)."""
+    f = np.asarray(ref)
+    if changed is not None:
+        f = f[changed]
+    return float(np.mean((f <= 0) | (f >= 255))) if f.size else 0.0
+
+
+def rmbe_covered(H, W):
+    """Boolean [H, W]: the pixels inside a window of either pass (every other pixel the oracle
+    leaves unchanged)."""
+    m = np.zeros((H, W), bool)
+    (h1, w1), (h2, w2) = rmbe_window_counts(H, W)
+    if h1 > 0 and w1 > 0:
+        m[:h1 * RMBE_P, RMBE_OFF:RMBE_OFF + w1 * RMBE_P] = True
+    if h2 > 0 and w2 > 0:
+        m[RMBE_OFF:RMBE_OFF + h2 * RMBE_P, :w2 * RMBE_P] = True
+    return m
+
+
 def set_options(codec, **kw):
     """Every structural option the parity tests vary, set explicitly (handles are shared)."""
     opts = {"streams": 2, "fuse01": -1, "fuse_tail": -1, "s1_form": -1, "s2_form": -1, "chain": 0, "chain_wh": 2,

@@ -124,25 +124,97 @@ def test_image_4k_properties(m3_256, rmbe_codec):
     """configs[4] at full size (3840x2160 -> 9 x 15 = 135 patches, 944 rmbe windows):
     symbol count, determinism, and the strips no rmbe window covers equal the unfiltered
     reconstruction (submit/2/rmbe/rmbe.py:70-111: rows >= 64 + 128 * 16 = 2112 and the
-    top-left 64x64 corner)."""
+    top-left 64x64 corner).  The launch sequence itself (shipped tunings: 68 + 67 patches per lane,
+    rmbe passes of 464 and 480 windows in chunks of 256) is compared bit for bit with the same
+    reconstruction built step by step on untuned, unfused handles (_image_4k_from_parts), and
+    roundtrip_device, the entry bench.py times, with both.  No oracle at this size: the oracle
+    meets these launches in test_gpu_product.py and the driver in test_gpu_rmbe.py."""
     from tf_image_compression_amd.image_codec import ImageCodec
     c3, _ = m3_256
     cr, _ = rmbe_codec
     H, W = 2160, 3840
     img = np.random.default_rng(4).integers(0, 256, (H, W, 3), dtype=np.uint8)
+    for c, name in ((c3, "model3_p256_b135_s2.json"), (cr, "model100_p128_b256_s2.json")):
+        assert c.tuning_source.startswith("shipped tuning:") and name in c.tuning_source, c.tuning_source
+    for n in (68, 67):  # the 135 patches on two lanes
+        k = c3.layer_kernels(n)
+        assert k[0].startswith("enc01_kernel") and k[-2].startswith("dec10_kernel"), (n, k)
     ic = ImageCodec(c3, cr)
     try:
+        for c in (c3, cr):
+            c.set_option("poison", 1)
         sym = ic.encode_image(img)
         assert sym.shape == (135, 16, 16, 80) and int(sym.max()) <= 1
         rec = ic.decode_image(sym, H, W, post_filter=True)
         plain = ic.decode_image(sym, H, W, post_filter=False)
         assert np.array_equal(ic.encode_image(img), sym)
         assert np.array_equal(ic.decode_image(sym, H, W, post_filter=True), rec)
+        # roundtrip_device, the entry bench.py times (no other test runs it at this size)
+        d_img, d_sym, d_out = c3.alloc(img.nbytes), c3.alloc(sym.nbytes), c3.alloc(img.nbytes)
+        d_img.upload(img)
+        c3.memset_device(d_sym, 0xA5, sym.nbytes)
+        c3.memset_device(d_out, 0x5A, img.nbytes)
+        ic.roundtrip_device(d_img, H, W, d_sym, d_out, post_filter=True)
+        ic.synchronize()
+        rt_sym, rt_rec = d_sym.download(sym.shape, np.uint8), d_out.download(img.shape, np.uint8)
+        for d in (d_img, d_sym, d_out):
+            d.free()
     finally:
+        for c in (c3, cr):
+            c.set_option("poison", 0)
         ic.close()
     assert np.array_equal(rec[2112:], plain[2112:])
     assert np.array_equal(rec[:64, :64], plain[:64, :64])
     assert not np.array_equal(rec[:2112], plain[:2112])  # the filter did run elsewhere
+    assert np.array_equal(rt_sym, sym) and np.array_equal(rt_rec, rec)
+    assert np.array_equal(_image_4k_from_parts(img, sym), rec)
+
+
+def _image_4k_from_parts(img, sym):
+    """The post-filtered reconstruction of `img` built from the steps the suite checks one by one,
+    on untuned handles with every fusion off, in the shipped forms (model_3: F(4x4,3x3) and
+    polyphase stride-2; rmbe: F(4x4,3x3)): tile, encode, decode to float, stitch, the two rmbe
+    passes, round.  Asserts that the encoder gives `sym`."""
+    from gpu_checks import poisoned
+    from tf_image_compression_amd.codec import Codec
+    from tf_image_compression_amd.topology import RMBE_ID
+    from tf_image_compression_amd.weights import synthetic_params, SYNTH_MEAN, SYNTH_STD
+    H, W, _ = img.shape
+    P, n = 256, sym.shape[0]
+    p3 = poisoned(Codec(3, synthetic_params(3, seed=0), SYNTH_MEAN, SYNTH_STD, patch_size=P, tuning="none"))
+    pr = poisoned(Codec(RMBE_ID, synthetic_params(RMBE_ID, seed=0), SYNTH_MEAN, SYNTH_STD, patch_size=128,
+                        tuning="none"))
+    try:
+        for c in (p3, pr):
+            for key in ("fuse01", "fuse_tail", "chain"):
+                c.set_option(key, 0)
+            c.set_option("s1_form", 2)
+        p3.set_option("s2_form", 1)
+        pr.set_option("s2_form", 0)
+        # each rmbe pass (464 and 480 windows) as ONE chunk here, where the tuned handle cuts it
+        # into 256 + 208 / 256 + 224: the comparison covers the driver's loop over chunks too
+        pr.set_option("chunk", 1024)
+        for c, nl in ((p3, 68), (pr, 128)):
+            k = c.layer_kernels(nl)
+            assert all(k) and not any("enc01" in x or "dec10" in x or "wino_chain" in x for x in k), k
+            assert any("wino4" in x for x in k), k
+        d_img, d_pat = p3.alloc(img.nbytes), p3.alloc(n * P * P * 3)
+        d_sym, d_f = p3.alloc(sym.nbytes), p3.alloc(n * P * P * 3 * 4)
+        d_fimg, d_out = p3.alloc(H * W * 3 * 4), p3.alloc(H * W * 3)
+        d_img.upload(img)
+        p3.image_to_patches_device(d_img, H, W, P, d_pat)
+        p3.encode_device(d_pat, n, d_sym)
+        p3.decode_device(d_sym, n, None, d_f)
+        p3.patches_to_image_device(d_f, H, W, P, d_fimg)
+        p3.synchronize()
+        assert np.array_equal(d_sym.download(sym.shape, np.uint8), sym)
+        pr.rmbe_image_device(d_fimg, H, W)
+        pr.round_u8_device(d_fimg, H * W * 3, d_out)
+        pr.synchronize()
+        return d_out.download(img.shape, np.uint8)
+    finally:
+        pr.close()
+        p3.close()
 
 
 def test_sharded_world1_gpu():

@@ -226,7 +226,7 @@ def test_head_tail_and_last_layer_variants(handles, monkeypatch, model_id, P):
     # the fused head
     g.set_options(c, **dict(UNFUSED, fuse01=1))
     names = set()
-    for v in range(5):  # conv_rgb.hip enc01_variants()
+    for v in g.ENC01_VARIANTS:
         monkeypatch.setenv("TIC_ENC01_VARIANT", str(v))
         kern = c.layer_kernels(n_lane)
         if model_id in NO_ENC01:
@@ -236,12 +236,12 @@ def test_head_tail_and_last_layer_variants(handles, monkeypatch, model_id, P):
         names.add(kern[0])
         idx, pre = c.encode(x, return_preact=True)
         assert np.array_equal(pre, ref[1]) and np.array_equal(idx, ref[0]), v
-    assert len(names) == (0 if model_id in NO_ENC01 else 5), names
+    assert len(names) == (0 if model_id in NO_ENC01 else len(g.ENC01_VARIANTS)), names
     monkeypatch.delenv("TIC_ENC01_VARIANT")
     # the fused tail
     g.set_options(c, **dict(UNFUSED, fuse_tail=1))
     names = set()
-    for v in range(16):  # conv_rgb.hip dec10_variants(): PK x PF x TA x CMP
+    for v in g.DEC10_VARIANTS:
         monkeypatch.setenv("TIC_DEC10_VARIANT", str(v))
         kern = c.layer_kernels(n_lane)
         if model_id in NO_DEC10:
@@ -251,21 +251,21 @@ def test_head_tail_and_last_layer_variants(handles, monkeypatch, model_id, P):
         names.add(kern[L - 2])
         u8, f = c.decode(ref[0], return_float=True)
         assert np.array_equal(u8, ref[2]) and np.array_equal(f, ref[3]), v
-    assert len(names) == (0 if model_id in NO_DEC10 else 16), names
+    assert len(names) == (0 if model_id in NO_DEC10 else len(g.DEC10_VARIANTS)), names
     monkeypatch.delenv("TIC_DEC10_VARIANT")
     # the VALU last layer's tilings, the persistent ones also with several tiles per workgroup
     g.set_options(c, **UNFUSED)
     names = set()
-    for t in range(6):
+    for t in g.RGB_OUT_TILES:
         monkeypatch.setenv("TIC_RGB_OUT_TILE", str(t))
         kern = c.layer_kernels(n_lane)
         assert re.fullmatch(r"convT_rgb_valu(_persist)?_kernel<\d+,\d+>", kern[L - 1]), kern
-        assert ("_persist" in kern[L - 1]) == (t >= 3), kern
+        assert ("_persist" in kern[L - 1]) == (t >= g.RGB_OUT_PERSISTENT_FROM), kern
         names.add(kern[L - 1])
-        for grid in ((0, 7) if t >= 3 else (0,)):
+        for grid in ((0, 7) if t >= g.RGB_OUT_PERSISTENT_FROM else (0,)):
             c.set_option("persist_grid", grid)
             u8, f = c.decode(ref[0], return_float=True)
             c.set_option("persist_grid", 0)
             assert np.array_equal(u8, ref[2]) and np.array_equal(f, ref[3]), (t, grid)
-    assert len(names) == 6, names
+    assert len(names) == len(g.RGB_OUT_TILES), names
     g.set_options(c)

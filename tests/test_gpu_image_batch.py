@@ -5,8 +5,8 @@
   restatement of utils.crop_image_input_patches / concat_patches per image, for offsets of any
   alignment, order and gaps, and nothing outside the images is written;
 * the ragged rmbe passes give every image bit-identically what tic_rmbe_image_device gives it
-  alone (patches are independent of how a batch is split), and stay within the whole-image bar
-  of test_gpu_image.py (2e-3 on the [0,255] scale) of the oracle;
+  alone (patches are independent of how a batch is split), and stay within the whole-image bars
+  of test_gpu_image.py (gpu_checks.float_bar / wino4_float_bar of the two-pass E32) of the oracle;
 * the list forms and the CLIs with --batch-images > 1 give byte for byte what the single-image
   forms give.
 """
@@ -16,6 +16,7 @@ import os
 import numpy as np
 import pytest
 
+from gpu_checks import float_bar, rmbe_image_reference, wino4_float_bar
 from oracle import tic_oracle as o
 
 pytestmark = pytest.mark.gpu
@@ -196,7 +197,6 @@ def _rmbe_case(cr, sizes, gap, check=None):
 
 
 def test_ragged_rmbe(codecs):
-    from tf_image_compression_amd.weights import SYNTH_MEAN, SYNTH_STD
     _, cr, _, pr = codecs
     # (128,192): a pass-1 window only; (100,500) and (64,700): no window in either pass
     # ((64-64)//128 == 0 rows); (256,256): 2x1 then 1x2 windows
@@ -205,8 +205,20 @@ def test_ragged_rmbe(codecs):
     assert np.array_equal(outs[2], imgs[2]) and np.array_equal(outs[4], imgs[4])
     assert not np.array_equal(outs[1], imgs[1])
     assert np.array_equal(outs[1][:, :64], imgs[1][:, :64])
-    ref = o.rmbe(imgs[0], pr, SYNTH_MEAN, SYNTH_STD)
-    assert float(np.max(np.abs(outs[0] - ref))) <= 2e-3
+    # the bars of test_gpu_rmbe.py: the direct form of the same ragged call within 4 E32, the
+    # default F(4x4,3x3) within wino4_float_bar of the direct form's error
+    ref, e32 = rmbe_image_reference(pr, imgs[0])
+    assert any("wino4" in k for k in cr.layer_kernels(1))
+    try:
+        cr.set_option("s1_form", 0)
+        _, direct = _rmbe_case(cr, sizes, gap=3, check=set())
+    finally:
+        cr.set_option("s1_form", -1)
+    err_direct = float(np.max(np.abs(direct[0].astype(np.float64) - ref)))
+    err = float(np.max(np.abs(outs[0].astype(np.float64) - ref)))
+    print(f"\nragged rmbe: E32 {e32:.3e} direct {err_direct:.3e} default {err:.3e}")
+    assert err_direct <= float_bar(e32), (err_direct, e32)
+    assert err <= wino4_float_bar(err_direct), (err, err_direct)
 
 
 def test_ragged_rmbe_more_images_than_one_launch_holds(codecs):

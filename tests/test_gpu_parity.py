@@ -12,7 +12,8 @@ import numpy as np
 import pytest
 
 from conftest import structured_patches
-from gpu_checks import check_codec as _check_codec, codec_mean, codec_std, poisoned  # noqa: F401
+from gpu_checks import (check_codec as _check_codec, codec_mean, codec_std, float_bar, poisoned,  # noqa: F401
+                        rmbe_reference, wino4_float_bar)
 from oracle import tic_oracle as o
 
 pytestmark = pytest.mark.gpu
@@ -352,9 +353,19 @@ def test_rmbe_network(lib_codec):
     r = np.random.default_rng(3)
     win = np.clip(r.normal(120, 50, (3, 128, 128, 3)), 0, 255).astype(np.float32)
     with poisoned(Codec(RMBE_ID, params, SYNTH_MEAN, SYNTH_STD, patch_size=128)) as c:
+        assert any("wino4" in k for k in c.layer_kernels(2))  # the net's default form is F(4x4,3x3)
         got = c.rmbe_windows(win)
-    ref = o.rmbe_model(params, SYNTH_MEAN, SYNTH_STD, win)
-    assert float(np.max(np.abs(got - ref))) <= 2e-3
+        c.set_option("s1_form", 0)
+        assert not any("wino" in k for k in c.layer_kernels(2))
+        direct = c.rmbe_windows(win)
+    # the bars of test_gpu_rmbe.py: the direct form within 4 E32 of the reference's own f32 error,
+    # F(4x4,3x3) within wino4_float_bar of the direct form's error (E32 is 6.1e-5 on this input)
+    ref, e32 = rmbe_reference(params, win)
+    err_direct = float(np.max(np.abs(direct.astype(np.float64) - ref)))
+    err = float(np.max(np.abs(got.astype(np.float64) - ref)))
+    print(f"\nrmbe network: E32 {e32:.3e} direct {err_direct:.3e} default {err:.3e}")
+    assert err_direct <= float_bar(e32), (err_direct, e32)
+    assert err <= wino4_float_bar(err_direct), (err, err_direct)
 
 
 @pytest.mark.parametrize("name", ["model0_p64.npz", "model3_p64.npz", "model1_p32.npz", "model2_p32.npz",

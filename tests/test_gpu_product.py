@@ -6,7 +6,8 @@ it, or directly — applies the shipped tuning database (tf_image_compression_am
 so it launches exactly the kernel sequence bench.py times: enc01_kernel, the tuned
 per-layer tilings, wino_chain_kernel (model_0) and dec10_kernel.  These tests run THAT
 sequence (batch 64 = the tuned per-lane batch of 32 on two lanes; model_3 batch 256 = 128
-per lane) against the oracle and the committed golden fixture, and bit for bit against the
+per lane; the 4K image's 135 patches = 68 + 67 and its rmbe passes of 464 and 480 windows; ch_128
+at batch 64: every state under tune/) against the oracle and the committed golden fixture, and bit for bit against the
 unfused, heuristically tiled path.  Plus the lane-ordering contract of successive device
 calls with different batch splits.
 Bars: tests/gpu_checks.py."""
@@ -222,3 +223,135 @@ def test_chain_shortened_where_a_long_run_cannot_be_resident():
         assert np.array_equal(pre, pre0) and np.array_equal(idx, idx0) and np.array_equal(rgb, rgb0)
         c.set_option("chain", -1)
         c.set_option("s1_form", -1)
+
+
+# ---------------------------------------------------------------------------
+# The other three shipped states, as bench.py times them (configs[4]'s 135 patches and its rmbe
+# passes, base_model/ch_128 at batch 64)
+# ---------------------------------------------------------------------------
+def _shipped_lines(model_id, P, name):
+    """The per-layer lines of one shipped state, stamp checked: what tuning_export must hold."""
+    from tf_image_compression_amd import tuning
+    docs = [e for e in tuning.entries(model_id, P, 2) if os.path.basename(e[1]) == name]
+    assert len(docs) == 1, name
+    assert docs[0][2]["_meta"]["source_sha256"] == tuning.source_digest(), f"{name}: stale stamp"
+    return [ln for ln in docs[0][2]["tuning"].splitlines()[1:] if ln and not ln.startswith("flag ")]
+
+
+def _assert_applied(c, model_id, P, name):
+    assert c.tuning_source.startswith("shipped tuning:") and name in c.tuning_source, c.tuning_source
+    exported = set(c.tuning_export().splitlines())
+    missing = [ln for ln in _shipped_lines(model_id, P, name) if ln not in exported]
+    assert not missing, (name, missing)
+
+
+def test_tuned_model3_p256_batch135_vs_oracle_and_plain():
+    """configs[4]'s codec step exactly as timed (model_3, P = 256, the 4K image's 135 patches =
+    lanes of 68 and 67, shipped tuning model3_p256_b135_s2.json): oracle on two patches, all 135
+    equal to the unfused, untuned path."""
+    from tf_image_compression_amd.codec import Codec
+    from tf_image_compression_amd.weights import synthetic_params, SYNTH_MEAN, SYNTH_STD
+    params = synthetic_params(3, seed=0)
+    with poisoned(Codec(3, params, SYNTH_MEAN, SYNTH_STD, patch_size=256)) as c:
+        _assert_applied(c, 3, 256, "model3_p256_b135_s2.json")
+        for n in (68, 67):
+            k = c.layer_kernels(n)
+            assert k[0].startswith("enc01_kernel") and k[1] == "" and k[-2].startswith("dec10_kernel") \
+                and k[-1] == "", (n, k)
+            assert any("wino4" in x for x in k), (n, k)
+        x = np.concatenate([structured_patches(2, 256, seed=1121),
+                            np.random.default_rng(1122).integers(0, 256, (133, 256, 256, 3), dtype=np.uint8)])
+        idx, rgb = check_codec_subset(c, params, 3, 256, x, k=2)
+    plain = _plain_codec(3, params, 256)
+    try:
+        kp = _kernels_of(plain, 68)
+        assert "enc01" not in kp and "dec10" not in kp and "wino_chain" not in kp, kp
+        assert np.array_equal(plain.encode(x), idx)
+        assert np.array_equal(plain.decode(idx), rgb)
+    finally:
+        plain.close()
+
+
+def test_tuned_ch128_p256_batch64_vs_oracle_and_plain():
+    """base_model/ch_128 exactly as timed (P = 256, batch 64 = two lanes of 32, shipped tuning
+    model128_p256_b64_s2.json: F(2x2,3x3) for the 128-wide stride-1 layers, direct stride-2 and
+    transposed layers; the net has none of the fused head's or tail's widths): oracle on two
+    patches, all 64 equal to the untuned path in the same forms."""
+    from tf_image_compression_amd.codec import Codec
+    from tf_image_compression_amd.topology import CH128_ID
+    from tf_image_compression_amd.weights import synthetic_params, SYNTH_MEAN, SYNTH_STD
+    params = synthetic_params(CH128_ID, seed=0)
+    with poisoned(Codec(CH128_ID, params, SYNTH_MEAN, SYNTH_STD, patch_size=256)) as c:
+        _assert_applied(c, CH128_ID, 256, "model128_p256_b64_s2.json")
+        exported = c.tuning_export().splitlines()
+        assert "flag s1_form 1" in exported and "flag s2_form 0" in exported, exported
+        k = c.layer_kernels(32)
+        assert all(k) and any(x.startswith("conv3x3_wino_kernel<128,128,") for x in k), k
+        assert not any("pwino" in x or "wino4" in x for x in k), k
+        x = np.concatenate([structured_patches(2, 256, seed=1131),
+                            np.random.default_rng(1132).integers(0, 256, (62, 256, 256, 3), dtype=np.uint8)])
+        idx, rgb = check_codec_subset(c, params, CH128_ID, 256, x, k=2)
+    plain = _plain_codec(CH128_ID, params, 256)
+    try:
+        plain.set_option("s1_form", 1)  # bit identity holds within a form only: the shipped flags' values
+        plain.set_option("s2_form", 0)
+        kp = plain.layer_kernels(32)
+        assert all(kp) and any(x.startswith("conv3x3_wino_kernel<128,128,") for x in kp), kp
+        assert not any("pwino" in x or "wino4" in x for x in kp), kp
+        assert np.array_equal(plain.encode(x), idx)
+        assert np.array_equal(plain.decode(idx), rgb)
+    finally:
+        plain.close()
+
+
+def test_tuned_rmbe_p128_as_the_4k_image_drives_it():
+    """configs[4]'s post-filter exactly as timed (the rmbe net, shipped tuning
+    model100_p128_b256_s2.json): the two pass sizes of 3840 x 2160, 464 and 480 windows, each run as
+    chunks of 256 + 208 / 256 + 224 over two lanes (per-launch batches 128, 104 and 112).  Oracle on
+    the first two windows, the second chunk's first and the last two of each call, at the bars of
+    test_gpu_rmbe.py for F(4x4,3x3); every window bit-identical to the unfused, untuned path of the
+    same form at chunk 256 and at chunk 8 (58 and 60 chunks)."""
+    from gpu_checks import (RMBE_4K_PASSES, float_bar, rmbe_params, rmbe_pass_checked, rmbe_pass_windows,
+                            rmbe_reference, wino4_float_bar)
+    from tf_image_compression_amd.codec import Codec
+    from tf_image_compression_amd.topology import RMBE_ID
+    from tf_image_compression_amd.weights import SYNTH_MEAN, SYNTH_STD
+    params = rmbe_params()
+    w = rmbe_pass_windows(max(RMBE_4K_PASSES))
+    outs = {}
+    with poisoned(Codec(RMBE_ID, params, SYNTH_MEAN, SYNTH_STD, patch_size=128)) as c:
+        _assert_applied(c, RMBE_ID, 128, "model100_p128_b256_s2.json")
+        for n in (128, 104, 112):
+            k = c.layer_kernels(n)
+            assert k[0].startswith("enc01_kernel<32,64,") and k[1] == "" and k[4].startswith("dec10_kernel<64,32,") \
+                and k[5] == "", (n, k)
+            assert k[2].startswith("conv3x3_wino4_kernel<64,64,") and k[3].startswith("conv3x3_wino4_kernel<64,64,"), k
+        for n in RMBE_4K_PASSES:
+            outs[n] = c.rmbe_windows(w[:n])
+    plain = poisoned(Codec(RMBE_ID, params, SYNTH_MEAN, SYNTH_STD, patch_size=128, tuning="none"))
+    try:
+        for key in ("fuse01", "fuse_tail", "chain"):
+            plain.set_option(key, 0)
+        plain.set_option("s1_form", 2)  # as shipped
+        kp = plain.layer_kernels(128)
+        assert all(kp) and kp[2].startswith("conv3x3_wino4_kernel<64,64,"), kp
+        for chunk in (256, 8):
+            plain.set_option("chunk", chunk)
+            for n in RMBE_4K_PASSES:
+                assert np.array_equal(plain.rmbe_windows(w[:n]), outs[n]), (chunk, n)
+        # the direct form's error on the checked windows: F(4x4,3x3)'s bar is stated against it
+        plain.set_option("chunk", 256)
+        plain.set_option("s1_form", 0)
+        assert not any("wino" in x for x in plain.layer_kernels(3))
+        for n in RMBE_4K_PASSES:
+            sel = rmbe_pass_checked(n)
+            ref, e32 = rmbe_reference(params, w[sel])
+            direct = plain.rmbe_windows(w[sel])
+            err_direct = float(np.max(np.abs(direct.astype(np.float64) - ref)))
+            err = float(np.max(np.abs(outs[n][sel].astype(np.float64) - ref)))
+            print(f"\nrmbe pass of {n}: E32 {e32:.3e} direct {err_direct:.3e} ({err_direct / e32:.2f} E32) "
+                  f"shipped {err:.3e} ({err / e32:.2f} E32)")
+            assert err_direct <= float_bar(e32), (n, err_direct, e32)
+            assert err <= wino4_float_bar(err_direct), (n, err, err_direct)
+    finally:
+        plain.close()

@@ -85,3 +85,69 @@ def test_geometry_sweep_inputs(model_id, P):
     print(f"\ngeometry model {model_id} P {P}: band share {band:.2e} clipped share {share:.2e} span {span:.1f}")
     assert band <= 1e-3, band
     assert share <= 1e-3, share
+
+
+# ---------------------------------------------------------------------------
+# The rmbe net and the whole-image driver (test_gpu_rmbe.py, test_gpu_product.py): what the float
+# bars of those tests cannot see is capped here, on the oracle alone
+# (submit/2/rmbe/model.py:113-197, rmbe.py:15-111).
+# ---------------------------------------------------------------------------
+def test_rmbe_net_windows_inputs():
+    """The structured, Gaussian and all-0 windows (the float bar's set): at most 1e-3 of the
+    oracle's outputs exactly 0 or 255, E32 > 0.  The all-255 window is an input like the others but
+    12.6 % of its outputs clip at 0: the GPU tests hold it to the bar of its own E32 and to bit
+    identity, and it stays out of this share."""
+    params = g.rmbe_params()
+    w = g.rmbe_net_windows()
+    assert w.shape == (5, 128, 128, 3) and w.dtype == np.float32
+    assert np.all(w[3] == 0) and np.all(w[4] == 255) and w[:3].std(axis=(1, 2, 3)).min() > 10
+    ref, e32 = g.rmbe_reference(params, w[g.RMBE_NET_FLOAT])
+    share = g.rmbe_clipped_share(ref)
+    ref255, e255 = g.rmbe_reference(params, w[g.RMBE_NET_FLAT255])
+    print(f"\nrmbe net windows: E32 {e32:.3e} clipped share {share:.2e}; all-255 window: E32 {e255:.3e} "
+          f"clipped share {g.rmbe_clipped_share(ref255):.2e}")
+    assert share <= 1e-3, share
+    assert e32 > 0 and e255 > 0
+    assert float(ref.max() - ref.min()) >= 100
+
+
+def test_rmbe_pass_windows_inputs():
+    """The windows test_gpu_product.py compares with the oracle at the 4K image's pass sizes (the
+    first two, the second chunk's first and the last two of 464 and of 480): structured and noise, nothing clipped."""
+    params = g.rmbe_params()
+    w = g.rmbe_pass_windows(480)
+    for n in g.RMBE_4K_PASSES:
+        sel = g.rmbe_pass_checked(n)
+        assert sel[:2] == [0, 1] and sel[-2:] == [n - 2, n - 1] and 256 in sel
+        ref, e32 = g.rmbe_reference(params, w[sel])
+        share = g.rmbe_clipped_share(ref)
+        print(f"\nrmbe pass of {n} windows: E32 {e32:.3e} clipped share {share:.2e}")
+        assert share <= 1e-3 and e32 > 0
+    # 3840 x 2160: the two pass sizes, and the handle's chunk of 256 cuts both
+    assert [a * b for a, b in g.rmbe_window_counts(2160, 3840)] == list(g.RMBE_4K_PASSES) == [464, 480]
+
+
+@pytest.mark.parametrize("H,W", list(g.RMBE_IMAGES), ids=[f"{H}x{W}" for H, W in g.RMBE_IMAGES])
+def test_rmbe_image_inputs(H, W):
+    """Every whole-image case has the window counts its comment names; among the pixels inside a
+    window at most 1e-3 of the oracle's outputs are exactly 0 or 255; E32 > 0 wherever a window
+    exists (191 x 191 has none: that case is bit identity with the input, not a float bar); and
+    the oracle leaves every pixel outside the windows as it is."""
+    want = g.RMBE_IMAGES[(H, W)]
+    got = g.rmbe_window_counts(H, W)
+    assert [a * b for a, b in got] == [a * b for a, b in want], (got, want)
+    for (a, b), (c, d) in zip(got, want):
+        assert a * b == 0 or (a, b) == (c, d)
+    img = g.rmbe_image(H, W)
+    assert img.shape == (H, W, 3) and img.dtype == np.float32
+    ref, e32 = g.rmbe_image_reference(g.rmbe_params(), img)
+    cov = g.rmbe_covered(H, W)
+    share = g.rmbe_clipped_share(ref, cov)
+    print(f"\nrmbe image {H}x{W}: windows {got} E32 {e32:.3e} clipped share {share:.2e}")
+    assert np.array_equal(ref[~cov], img[~cov])
+    if sum(a * b for a, b in got) == 0:
+        assert not cov.any() and np.array_equal(ref, img)
+        return
+    assert share <= 1e-3, share
+    assert e32 > 0
+    assert float(np.mean(ref[cov] != img[cov])) > 0.99  # the filter does change what it covers
