@@ -51,11 +51,20 @@ RCSEG_BIN := $(BUILD)/rcseg_fuzz_asan
 asan-rcseg: $(RCSEG_BIN)
 	$(RCSEG_BIN) $(BUILD)
 
-$(RCSEG_BIN): tests/native/rcseg_fuzz.cpp $(CSRC)/range_coder.cpp include/tic.h | $(BUILD)
+$(RCSEG_BIN): tests/native/rcseg_fuzz.cpp $(CSRC)/range_coder.cpp $(CSRC)/host_util.cpp include/tic.h | $(BUILD)
 	g++ -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=all \
-	    -Iinclude -o $@ tests/native/rcseg_fuzz.cpp $(CSRC)/range_coder.cpp
+	    -Iinclude -o $@ tests/native/rcseg_fuzz.cpp $(CSRC)/range_coder.cpp $(CSRC)/host_util.cpp
+
+# The version-2 (context) container entries (tic_rcseg_*_ctx; their table CRC is host_util.cpp's).
+RCSEG_CTX_BIN := $(BUILD)/rcseg_ctx_fuzz_asan
+asan-rcseg-ctx: $(RCSEG_CTX_BIN)
+	$(RCSEG_CTX_BIN) $(BUILD)
+
+$(RCSEG_CTX_BIN): tests/native/rcseg_ctx_fuzz.cpp $(CSRC)/range_coder.cpp $(CSRC)/host_util.cpp include/tic.h | $(BUILD)
+	g++ -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=all \
+	    -Iinclude -o $@ tests/native/rcseg_ctx_fuzz.cpp $(CSRC)/range_coder.cpp $(CSRC)/host_util.cpp
 
 clean:
 	rm -rf $(BUILD) $(LIB)
 
-.PHONY: all clean asan asan-rcseg
+.PHONY: all clean asan asan-rcseg asan-rcseg-ctx

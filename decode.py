@@ -48,6 +48,11 @@ def my_parse_args(argv=None):
     args = p.parse_args(argv)
     if args.entropy == "device" and args.raw:
         p.error("--raw files hold no entropy-coded stream: it cannot be combined with --entropy device")
+    if args.entropy == "host" and not args.raw:
+        from tf_image_compression_amd.range_coder import dist_is_ctx
+        if dist_is_ctx(args.dist.format(args.model_num)):
+            p.error(f"{args.dist.format(args.model_num)} holds per-context probabilities (2-D): the single-stream "
+                    "host coder has one table; use --entropy device")
     return args
 
 
@@ -78,6 +83,22 @@ def apply_range_decoder(seq_len, path, cum_freq):
     return out
 
 
+def check_container_version(path, stream, cum_freq, args):
+    """The coder follows the file's version byte: version 1 was coded under one table (a 1-D
+    --dist array), version 2 under per-context tables (a 2-D one)."""
+    from tf_image_compression_amd import entropy
+    if not entropy.is_container(stream):
+        return  # entropy.parse names what it is not
+    version, ctx = entropy.container_version(stream), entropy.is_ctx_table(cum_freq)
+    dist = args.dist.format(args.model_num)
+    if version == 2 and not ctx:
+        raise ValueError(f"{path} is a version-2 (context) stream, but {dist} holds one 1-D table: pass the "
+                         "2-D per-context distribution it was encoded with")
+    if version == 1 and ctx:
+        raise ValueError(f"{path} is a version-1 (single-table) stream, but {dist} holds 2-D per-context "
+                         "tables: pass the 1-D distribution it was encoded with")
+
+
 def load_model(args, config):
     from tf_image_compression_amd.weights import load_normalization, synthetic_params
     import importlib
@@ -105,9 +126,9 @@ def uncompress(model, args):
                          f"at patch {P}: {codec.code_shape}")
     cum_freq = None
     if not args.raw:
-        from tf_image_compression_amd.range_coder import symbol_table
-        cum_freq = symbol_table(np.load(args.dist.format(args.model_num), allow_pickle=False),
-                                resolution=config["resolution"])
+        from tf_image_compression_amd.range_coder import dist_table
+        cum_freq = dist_table(np.load(args.dist.format(args.model_num), allow_pickle=False),
+                              resolution=config["resolution"])
     post = None
     if args.rmbe:
         from tf_image_compression_amd.rmbe import RmbeFilter
@@ -147,6 +168,8 @@ def uncompress(model, args):
         sizes = [get_img_info(f, config)[1:] for f in filenames]
         for group in ic.plan_batches(sizes, P, args.batch_images):
             streams = [(Path(input_dir) / filenames[i]).read_bytes() for i in group]
+            for i, stream in zip(group, streams):
+                check_container_version(str(Path(input_dir) / filenames[i]), stream, cum_freq, args)
             images = ic.decode_streams_to_images(streams, [sizes[i] for i in group], cum_freq,
                                                  post_filter=post is not None)
             for i, recons in zip(group, images):

@@ -15,7 +15,10 @@ no checkpoint exists), ``--raw`` (store bit-packed symbols, no entropy coding),
 ``--batch-images N`` (N > 1: consecutive images share one patch batch, image_codec.py),
 ``--entropy device`` (the symbols stay on the GPU and are range-coded there, one segment of
 ``--segment L`` symbols per lane; each file then holds one segmented-stream container,
-tf_image_compression_amd/entropy.py, which ``decode.py --entropy device`` reads).
+tf_image_compression_amd/entropy.py, which ``decode.py --entropy device`` reads).  With
+``--entropy device`` a 2-D ``--dist`` array ([K, Q] per-context probabilities,
+get_encoded_distribution.py --context) codes symbol k of an image under table k mod K and writes
+version-2 containers.
 """
 import argparse
 import os
@@ -59,12 +62,17 @@ def my_parse_args(argv=None):
     args = p.parse_args(argv)
     if args.entropy == "device" and args.raw:
         p.error("--raw stores symbols without entropy coding: it cannot be combined with --entropy device")
+    if args.entropy == "host" and not args.raw:
+        from tf_image_compression_amd.range_coder import dist_is_ctx
+        if dist_is_ctx(args.dist.format(args.model_num)):
+            p.error(f"{args.dist.format(args.model_num)} holds per-context probabilities (2-D): the single-stream "
+                    "host coder has one table; use --entropy device")
     return args
 
 
 def symbol_table(args, config):
     """encode.py:77-86: prob -> prob*resolution+1 -> renormalise -> prob_to_cum_freq."""
-    from tf_image_compression_amd.range_coder import symbol_table as table
+    from tf_image_compression_amd.range_coder import dist_table as table
     path = args.dist.format(args.model_num)
     prob = np.load(path, allow_pickle=False)
     return table(prob, resolution=config["resolution"])

@@ -14,7 +14,9 @@ MS-SSIM (images with a side below 161 have none and are left out) and total esti
 total pixels.  Without a distribution file the rate columns are omitted.  ``--entropy device``
 (with ``--segment L``) also range-codes every image's symbols on the GPU into a segmented
 stream (tf_image_compression_amd/entropy.py) and prints its real size, ``coded_bytes``, and the
-bpp from it.
+bpp from it.  With ``--entropy device`` a 2-D ``--dist`` array ([K, Q] per-context probabilities,
+get_encoded_distribution.py --context) gives both under the context coder: the estimate from
+the per-context histogram, ``coded_bytes`` from version-2 containers.
 """
 import argparse
 import json
@@ -56,6 +58,10 @@ def my_parse_args(argv=None):
     args = p.parse_args(argv)
     if args.batch_images < 1:
         p.error("--batch-images must be at least 1")
+    if args.entropy == "host":
+        from tf_image_compression_amd.range_coder import dist_is_ctx
+        if dist_is_ctx(args.dist.format(args.model_num)):
+            p.error(f"{args.dist.format(args.model_num)} holds per-context probabilities (2-D): use --entropy device")
     return args
 
 
@@ -106,8 +112,10 @@ def run(model, args) -> dict:
     cum_freq = None
     dist = args.dist.format(args.model_num)
     if os.path.exists(dist):
-        from tf_image_compression_amd.range_coder import symbol_table
-        cum_freq = symbol_table(np.load(dist, allow_pickle=False), resolution=config["resolution"])
+        from tf_image_compression_amd.range_coder import dist_table
+        cum_freq = dist_table(np.load(dist, allow_pickle=False), resolution=config["resolution"])
+        if np.ndim(cum_freq) == 2 and getattr(args, "entropy", "host") != "device":
+            raise ValueError(f"{dist} holds per-context probabilities (2-D): use --entropy device")
     else:
         print(f"no symbol distribution at {dist}: the estimated rate is omitted")
     post = None

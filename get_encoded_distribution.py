@@ -10,6 +10,13 @@ encoded on the GPU and histogrammed on the GPU (tic_histogram_device accumulates
 device counter array); the counts come back once at the end.  ``-f/--model_file`` is
 accepted for flag compatibility (the model is chosen by ``-m``).  Extra optional flags as
 encode.py: ``--norm``, ``--synthetic-weights``.
+
+``--context channel`` / ``--context position`` also estimate a periodic context model (the
+reference computes the per-position probabilities, cal_encoded_distribution.py:113-160
+``seq_prob``, but its coder could not use them): one histogram per channel (K = C) or per code
+position (K = eh * ew * C) through tic_histogram_ctx_device, saved as a ``[K, Q]`` probability
+array to ``--context-output`` (``data_info/distribution_ctx_{}.npy``), which ``encode.py`` /
+``decode.py --entropy device --dist`` take.  The 1-D file is written as without the flag.
 """
 import argparse
 import os
@@ -42,7 +49,18 @@ def my_parse_args(argv=None):
                    help="File to keep encoded distribution info")
     p.add_argument("--norm", type=str, default="data_info/channel_normalization_params.npz")
     p.add_argument("--synthetic-weights", action="store_true")
+    p.add_argument("--context", choices=["none", "channel", "position"], default="none",
+                   help="also save per-context probabilities [K, Q]: one table per channel (K = C) or per "
+                        "code position (K = eh * ew * C)")
+    p.add_argument("--context-output", type=str, default="data_info/distribution_ctx_{}.npy",
+                   help="File for the per-context probabilities of --context")
     return p.parse_args(argv)
+
+
+def context_count(context, code_shape) -> int:
+    """K of --context for a code of shape (eh, ew, C): symbols are ordered patch, h, w, C."""
+    eh, ew, ec = (int(v) for v in code_shape)
+    return {"none": 1, "channel": ec, "position": eh * ew * ec}[context]
 
 
 def load_model(args):
@@ -57,21 +75,35 @@ def load_model(args):
 
 def encoded_frequencies(codec, patch_iter, Q):
     """Sum over batches of np.histogram(encoder(batch), range(Q+1))[0], on the GPU."""
+    return encoded_context_frequencies(codec, patch_iter, Q, None)[0]
+
+
+def encoded_context_frequencies(codec, patch_iter, Q, K):
+    """(freq [Q], ctx_freq [K, Q]): ``encoded_frequencies`` and, in the same pass, the counts of
+    symbol i of a batch in row i mod K (a batch holds whole patches, so it starts at context 0
+    for K = C and K = eh * ew * C).  ``K = None``: ctx_freq is None."""
     P = codec.patch_size
     eh, ew, ec = codec.code_shape
     d_in = codec.alloc(BATCH * P * P * 3)
     d_sym = codec.alloc(BATCH * eh * ew * ec)
     d_cnt = codec.alloc(8 * Q)
     codec.memset_device(d_cnt, 0, 8 * Q)
+    d_ctx = None
+    if K is not None:
+        d_ctx = codec.alloc(8 * K * Q)
+        codec.memset_device(d_ctx, 0, 8 * K * Q)
     for batch in patch_iter:
         x = np.ascontiguousarray(batch, np.uint8).reshape(-1, P, P, 3)
         d_in.upload(x)
         codec.encode_device(d_in, x.shape[0], d_sym)
         codec.histogram_device(d_sym, x.shape[0] * eh * ew * ec, Q, d_cnt)
+        if d_ctx is not None:
+            codec.histogram_ctx_device(d_sym, x.shape[0] * eh * ew * ec, Q, K, d_ctx)
     freq = d_cnt.download((Q,), np.uint64).astype(np.float64)
-    for b in (d_in, d_sym, d_cnt):
+    ctx_freq = None if d_ctx is None else d_ctx.download((K, Q), np.uint64).astype(np.float64)
+    for b in (d_in, d_sym, d_cnt) + (() if d_ctx is None else (d_ctx,)):
         b.free()
-    return freq
+    return freq, ctx_freq
 
 
 def patch_batches(paths, P):
@@ -90,12 +122,26 @@ def get_distribution(model, args):
     P, Q = config["patch_size"], config["quan_scale"]
     codec = model.codec(P, Q)
     paths = utils.read_image_list(args.data_list.format(P))
-    freq = encoded_frequencies(codec, patch_batches(paths, P), Q)
+    context = getattr(args, "context", "none")
+    if context == "none":
+        freq = encoded_frequencies(codec, patch_batches(paths, P), Q)
+    else:
+        K = context_count(context, codec.code_shape)
+        freq, ctx_freq = encoded_context_frequencies(codec, patch_batches(paths, P), Q, K)
     prob = freq / sum(freq)  # get_encoded_distribution.py:129
     print(prob)
     out = args.output_file.format(args.model_num)
     os.makedirs(os.path.dirname(out) or ".", exist_ok=True)
     np.save(out, prob)
+    if context != "none":
+        # a context no patch reached keeps the global distribution (symbol_table adds 1 to every
+        # frequency anyway, so no table entry is zero)
+        rows = ctx_freq.sum(axis=1, keepdims=True)
+        ctx_prob = np.where(rows > 0, ctx_freq / np.maximum(rows, 1), prob[None, :])
+        ctx_out = args.context_output.format(args.model_num)
+        os.makedirs(os.path.dirname(ctx_out) or ".", exist_ok=True)
+        np.save(ctx_out, ctx_prob)
+        print(f"{context} contexts: [{K}, {Q}] probabilities -> {ctx_out}")
     return prob
 
 

@@ -366,6 +366,31 @@ int tic_rcseg_parse(const uint8_t* buf, size_t nbytes, uint32_t* L, uint64_t* n)
 int tic_rcseg_decode(const uint8_t* buf, size_t nbytes, const int64_t* cum_freq, size_t ncum, uint8_t* sym_out,
                      size_t n);
 
+/* --- segmented range-coder stream, version 2: a periodic context model (host part) ---
+ * The stream is coded under K cumulative tables; symbol k of the stream uses table k mod K (K = the
+ * code's channel count: one table per channel; K = the symbols of a patch: one per code
+ * position; K = 1: the model of version 1).  The container is version 1 with a 28-byte header:
+ *   0..19  as version 1, version byte = 2
+ *   20 4   K                      24 4  CRC-32C (tic_crc32c) of the K*ncum table entries as int64,
+ *   28     the u16 length table, then the payloads        little-endian, row-major
+ * Segment j starts at context (j*L) mod K (K need not divide L); its payload is what
+ * tic_rc_encode writes when every symbol is passed in a call of its own with its context's table.
+ * tables: K rows of one common ncum (2..257), each row a table as version 1 asks for; rows may
+ * have different totals.  1 <= K <= 65536 and K*ncum <= 262144. */
+
+/* tic_rcseg_bound + 8. */
+int tic_rcseg_bound_ctx(size_t n, uint32_t L, size_t* bytes);
+/* As tic_rcseg_encode, under tables[K][ncum]. */
+int tic_rcseg_encode_ctx(const uint8_t* sym, size_t n, uint32_t L, const int64_t* tables, size_t K, size_t ncum,
+                         uint8_t* out, size_t cap, size_t* written);
+/* tic_rcseg_parse's validation of a version-2 container (a version-1 container is TIC_EINVAL, as
+ * a version-2 one is for tic_rcseg_parse); also the header's K and CRC.  Outputs may be NULL. */
+int tic_rcseg_parse_ctx(const uint8_t* buf, size_t nbytes, uint32_t* L, uint64_t* n, uint32_t* K, uint32_t* crc);
+/* tic_rcseg_parse_ctx, TIC_EINVAL when n, K or the CRC of `tables` differ from the header's, then
+ * the n symbols. */
+int tic_rcseg_decode_ctx(const uint8_t* buf, size_t nbytes, const int64_t* tables, size_t K, size_t ncum,
+                         uint8_t* sym_out, size_t n);
+
 /* --- segmented streams on the device (csrc/tic_entropy.cpp) ---
  * One range coder per lane, one segment each; a scan over the segment lengths; a gather that
  * writes the containers.  All entries are asynchronous on the handle's stream, never synchronise,
@@ -398,6 +423,31 @@ int tic_entropy_encode_device(tic_handle* h, const uint8_t* d_sym, const int64_t
 int tic_entropy_decode_device(tic_handle* h, const uint8_t* d_blob, const int64_t* blob_offsets,
                               const int64_t* blob_sizes, const int64_t* counts, int n_streams, uint8_t* d_sym,
                               const int64_t* sym_offsets, void* d_scratch, size_t scratch_bytes);
+
+/* --- version-2 (context) streams on the device ---
+ * The K tables of the following *_ctx_device calls on this handle, validated as
+ * tic_rcseg_encode_ctx does and uploaded to a device buffer the handle owns (freed by
+ * tic_destroy); the upload is ordered on the handle's stream and complete on return.
+ * Independent of tic_entropy_set_table: the version-1 entries keep their table.  The coder
+ * kernels stage the tables in LDS when K*ncum*4 <= 64 KiB and read them from global memory
+ * otherwise. */
+int tic_entropy_set_tables(tic_handle* h, const int64_t* tables, size_t K, size_t ncum);
+/* tic_entropy_encode_device writing version-2 containers under the tables set: the same
+ * arguments, scratch (tic_entropy_scratch_bytes) and contract, out_cap at least the sum of
+ * tic_rcseg_bound_ctx.  Every stream starts at context 0. */
+int tic_entropy_encode_ctx_device(tic_handle* h, const uint8_t* d_sym, const int64_t* sym_offsets,
+                                  const int64_t* counts, int n_streams, uint32_t L, void* d_scratch,
+                                  size_t scratch_bytes, uint8_t* d_out, size_t out_cap, uint64_t* d_sizes);
+/* tic_entropy_decode_device for version-2 containers (passed through tic_rcseg_parse_ctx by the
+ * caller).  A container whose version, K or CRC is not that of the tables set decodes to zeros,
+ * as one whose header does not fit counts[i]. */
+int tic_entropy_decode_ctx_device(tic_handle* h, const uint8_t* d_blob, const int64_t* blob_offsets,
+                                  const int64_t* blob_sizes, const int64_t* counts, int n_streams, uint8_t* d_sym,
+                                  const int64_t* sym_offsets, void* d_scratch, size_t scratch_bytes);
+/* tic_histogram_device per context: symbol i of d_sym[0..n) counts in row i mod K of the uint64
+ * counts d_counts[K][Q] (8-byte aligned; accumulates, zero it first; d_sym of any alignment).
+ * Integer adds only: the result does not depend on the order they happen in.  1 <= K <= 65536. */
+int tic_histogram_ctx_device(tic_handle* h, const uint8_t* d_sym, size_t n, int Q, int K, uint64_t* d_counts);
 
 #ifdef __cplusplus
 }

@@ -105,6 +105,21 @@ SIGNATURES = [
                                            vp, C.c_size_t, vp, C.c_size_t, vp]),
     ("tic_entropy_decode_device", C.c_int, [vp, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                            C.c_int, vp, C.POINTER(C.c_int64), vp, C.c_size_t]),
+    # version-2 (context) streams: K tables, symbol k under table k mod K
+    ("tic_rcseg_bound_ctx", C.c_int, [C.c_size_t, C.c_uint32, C.POINTER(C.c_size_t)]),
+    ("tic_rcseg_encode_ctx", C.c_int, [u8p, C.c_size_t, C.c_uint32, C.POINTER(C.c_int64), C.c_size_t, C.c_size_t, u8p,
+                                      C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("tic_rcseg_parse_ctx", C.c_int, [u8p, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
+                                     C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    ("tic_rcseg_decode_ctx", C.c_int, [u8p, C.c_size_t, C.POINTER(C.c_int64), C.c_size_t, C.c_size_t, u8p,
+                                      C.c_size_t]),
+    ("tic_entropy_set_tables", C.c_int, [vp, C.POINTER(C.c_int64), C.c_size_t, C.c_size_t]),
+    ("tic_entropy_encode_ctx_device", C.c_int, [vp, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int,
+                                               C.c_uint32, vp, C.c_size_t, vp, C.c_size_t, vp]),
+    ("tic_entropy_decode_ctx_device", C.c_int, [vp, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                               C.POINTER(C.c_int64), C.c_int, vp, C.POINTER(C.c_int64), vp,
+                                               C.c_size_t]),
+    ("tic_histogram_ctx_device", C.c_int, [vp, vp, C.c_size_t, C.c_int, C.c_int, vp]),
     ("tic_device_info", C.c_int, [vp, C.c_char_p, C.c_int]),
 ]
 

@@ -400,6 +400,45 @@ class Codec:
             ptr(soff, C.c_int64), d_scratch.ptr, d_scratch.nbytes if scratch_bytes is None else int(scratch_bytes)),
             "tic_entropy_decode_device")
 
+    # version-2 (context) streams: K tables, symbol k of a stream under table k mod K
+    def entropy_set_tables(self, tables) -> None:
+        """The ``[K, ncum]`` cumulative tables of the following ``*_ctx_device`` calls on this codec,
+        uploaded to the device (tic_entropy_set_tables); ``entropy_set_table``'s table is untouched."""
+        from .entropy import ctx_tables
+        t = ctx_tables(tables)
+        check(lib().tic_entropy_set_tables(self._h, ptr(t, C.c_int64), t.shape[0], t.shape[1]),
+              "tic_entropy_set_tables")
+
+    def entropy_encode_ctx_device(self, d_sym: DeviceBuffer, sym_offsets, counts, segment: int,
+                                  d_scratch: DeviceBuffer, d_out: DeviceBuffer, d_sizes: DeviceBuffer,
+                                  scratch_bytes: int | None = None, out_cap: int | None = None) -> None:
+        """``entropy_encode_device`` writing version-2 containers under the tables set
+        (tic_entropy_encode_ctx_device); every stream starts at context 0."""
+        n, (off, cnt) = self._stream_table(sym_offsets, counts)
+        if d_sizes.nbytes < 8 * n:
+            raise ValueError(f"d_sizes holds {d_sizes.nbytes} bytes, {n} streams need {8 * n}")
+        check(lib().tic_entropy_encode_ctx_device(
+            self._h, d_sym.ptr, ptr(off, C.c_int64), ptr(cnt, C.c_int64), n, int(segment), d_scratch.ptr,
+            d_scratch.nbytes if scratch_bytes is None else int(scratch_bytes), d_out.ptr,
+            d_out.nbytes if out_cap is None else int(out_cap), d_sizes.ptr), "tic_entropy_encode_ctx_device")
+
+    def entropy_decode_ctx_device(self, d_blob: DeviceBuffer, blob_offsets, blob_sizes, counts, d_sym: DeviceBuffer,
+                                  sym_offsets, d_scratch: DeviceBuffer, scratch_bytes: int | None = None) -> None:
+        """``entropy_decode_device`` for version-2 containers (validated by ``entropy.parse_ctx``
+        before the upload) under the tables set (tic_entropy_decode_ctx_device)."""
+        n, (boff, bsz, cnt, soff) = self._stream_table(blob_offsets, blob_sizes, counts, sym_offsets)
+        check(lib().tic_entropy_decode_ctx_device(
+            self._h, d_blob.ptr, ptr(boff, C.c_int64), ptr(bsz, C.c_int64), ptr(cnt, C.c_int64), n, d_sym.ptr,
+            ptr(soff, C.c_int64), d_scratch.ptr, d_scratch.nbytes if scratch_bytes is None else int(scratch_bytes)),
+            "tic_entropy_decode_ctx_device")
+
+    def histogram_ctx_device(self, d_sym: DeviceBuffer, n: int, Q: int, K: int, d_counts: DeviceBuffer):
+        """Accumulate the histogram of symbol ``i`` of ``d_sym[0..n)`` into row ``i mod K`` of the
+        uint64 counts ``d_counts[K, Q]`` (tic_histogram_ctx_device)."""
+        if d_counts.nbytes < 8 * int(K) * int(Q):
+            raise ValueError(f"d_counts holds {d_counts.nbytes} bytes, [{K}, {Q}] counts need {8 * int(K) * int(Q)}")
+        check(lib().tic_histogram_ctx_device(self._h, d_sym.ptr, n, Q, K, d_counts.ptr), "tic_histogram_ctx_device")
+
     def round_u8_device(self, d_in: DeviceBuffer, n: int, d_out: DeviceBuffer):
         check(lib().tic_round_u8_device(self._h, d_in.ptr, n, d_out.ptr), "tic_round_u8_device")
 

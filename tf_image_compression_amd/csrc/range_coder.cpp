@@ -185,6 +185,72 @@ int check_seg_table(const int64_t* cum, size_t ncum, int64_t* total) {
     if (cum[i] == cum[i - 1]) return rc_fail(TIC_EINVAL, "segmented streams need every frequency > 0");
   return TIC_OK;
 }
+
+// --- segmented stream, version 2: K tables, symbol k of the stream under table k mod K ---
+constexpr size_t kCtxHeader = 28;
+constexpr size_t kCtxMaxK = 65536, kCtxMaxEntries = 262144;
+
+// K rows of one ncum, each a check_seg_table table; totals[k] receives row k's total
+int check_ctx_tables(const int64_t* tables, size_t K, size_t ncum, std::vector<int64_t>* totals) {
+  if (!tables) return rc_fail(TIC_EINVAL, "invalid frequency table (null)");
+  if (K < 1 || K > kCtxMaxK)
+    return rc_fail(TIC_EINVAL, "context count " + std::to_string(K) + " must be in [1, 65536]");
+  if (ncum < 2) return rc_fail(TIC_EINVAL, "invalid frequency table (needs >= 2 entries)");
+  if (ncum > 257) return rc_fail(TIC_EINVAL, "segmented streams code byte symbols: at most 257 table entries");
+  if (K * ncum > kCtxMaxEntries)
+    return rc_fail(TIC_EINVAL, "context tables of " + std::to_string(K * ncum) + " entries exceed the limit of 262144");
+  totals->resize(K);
+  for (size_t k = 0; k < K; ++k) {
+    const int rc = check_seg_table(tables + k * ncum, ncum, &(*totals)[k]);
+    if (rc) {
+      g_rc_err = "context " + std::to_string(k) + ": " + g_rc_err;
+      return rc;
+    }
+  }
+  return TIC_OK;
+}
+
+// CRC-32C of the K * ncum int64 entries, little-endian, row-major
+uint32_t ctx_tables_crc(const int64_t* tables, size_t entries) {
+  uint32_t crc = 0;
+  uint8_t b[8 * 64];
+  for (size_t at = 0; at < entries; at += 64) {
+    const size_t m = std::min<size_t>(64, entries - at);
+    for (size_t i = 0; i < m; ++i)
+      for (int q = 0; q < 8; ++q) b[8 * i + q] = (uint8_t)((uint64_t)tables[at + i] >> (8 * q));
+    crc = tic_crc32c(b, 8 * m, crc);
+  }
+  return crc;
+}
+
+// The framing both versions share around their headers: L, n, the length table behind a header
+// of `header` bytes (nbytes >= header), the payload bytes.
+int parse_framing(const uint8_t* buf, size_t nbytes, size_t header, uint32_t* L_out, uint64_t* n_out) {
+  const uint32_t L = rd32(buf + 8);
+  const uint64_t n = rd64(buf + 12);
+  if (!seg_L_ok(L)) return rc_fail(TIC_EINVAL, "segmented stream: segment length " + std::to_string(L) + " must be a multiple of 4 in [4, 16384]");
+  if (n == 0) return rc_fail(TIC_EINVAL, "segmented stream: no symbols");
+  const uint64_t rest = nbytes - header;
+  if (n > (UINT64_MAX >> 3) || (n + L - 1) / L > rest / 2)
+    return rc_fail(TIC_EINVAL, "segmented stream: truncated inside the length table");
+  const uint64_t S = (n + L - 1) / L;
+  const uint8_t* lens = buf + header;
+  uint64_t sum = 0;
+  for (uint64_t j = 0; j < S; ++j) {
+    const uint64_t len = (uint64_t)lens[2 * j] | (uint64_t)lens[2 * j + 1] << 8;
+    const uint64_t cnt = j + 1 < S ? L : n - j * L;
+    if (len > 3 * cnt + 4)
+      return rc_fail(TIC_EINVAL, "segmented stream: segment " + std::to_string(j) + " claims " + std::to_string(len) +
+                                     " bytes for " + std::to_string(cnt) + " symbols");
+    sum += len;
+  }
+  if (sum != rest - 2 * S)
+    return rc_fail(TIC_EINVAL, "segmented stream: segment lengths sum to " + std::to_string(sum) + " bytes, " +
+                                   std::to_string(rest - 2 * S) + " follow the length table");
+  if (L_out) *L_out = L;
+  if (n_out) *n_out = n;
+  return TIC_OK;
+}
 }  // namespace
 
 struct tic_rc_encoder {
@@ -336,30 +402,7 @@ int tic_rcseg_parse(const uint8_t* buf, size_t nbytes, uint32_t* L_out, uint64_t
   if (memcmp(buf, kSegMagic, 4) != 0) return rc_fail(TIC_EINVAL, "not a segmented stream: magic is not \"TICS\"");
   if (buf[4] != 1) return rc_fail(TIC_EINVAL, "segmented stream version " + std::to_string(buf[4]) + " is not supported");
   if (buf[5] || buf[6] || buf[7]) return rc_fail(TIC_EINVAL, "segmented stream: reserved bytes are not zero");
-  const uint32_t L = rd32(buf + 8);
-  const uint64_t n = rd64(buf + 12);
-  if (!seg_L_ok(L)) return rc_fail(TIC_EINVAL, "segmented stream: segment length " + std::to_string(L) + " must be a multiple of 4 in [4, 16384]");
-  if (n == 0) return rc_fail(TIC_EINVAL, "segmented stream: no symbols");
-  const uint64_t rest = nbytes - kSegHeader;
-  if (n > (UINT64_MAX >> 3) || (n + L - 1) / L > rest / 2)
-    return rc_fail(TIC_EINVAL, "segmented stream: truncated inside the length table");
-  const uint64_t S = (n + L - 1) / L;
-  const uint8_t* lens = buf + kSegHeader;
-  uint64_t sum = 0;
-  for (uint64_t j = 0; j < S; ++j) {
-    const uint64_t len = (uint64_t)lens[2 * j] | (uint64_t)lens[2 * j + 1] << 8;
-    const uint64_t cnt = j + 1 < S ? L : n - j * L;
-    if (len > 3 * cnt + 4)
-      return rc_fail(TIC_EINVAL, "segmented stream: segment " + std::to_string(j) + " claims " + std::to_string(len) +
-                                     " bytes for " + std::to_string(cnt) + " symbols");
-    sum += len;
-  }
-  if (sum != rest - 2 * S)
-    return rc_fail(TIC_EINVAL, "segmented stream: segment lengths sum to " + std::to_string(sum) + " bytes, " +
-                                   std::to_string(rest - 2 * S) + " follow the length table");
-  if (L_out) *L_out = L;
-  if (n_out) *n_out = n;
-  return TIC_OK;
+  return parse_framing(buf, nbytes, kSegHeader, L_out, n_out);
 }
 
 int tic_rcseg_decode(const uint8_t* buf, size_t nbytes, const int64_t* cum, size_t ncum, uint8_t* sym_out, size_t n) {
@@ -388,5 +431,110 @@ int tic_rcseg_decode(const uint8_t* buf, size_t nbytes, const int64_t* cum, size
   return TIC_OK;
 }
 
-}  // extern "C"
+// --- segmented stream, version 2 ---
 
+int tic_rcseg_bound_ctx(size_t n, uint32_t L, size_t* bytes) {
+  const int rc = tic_rcseg_bound(n, L, bytes);
+  if (rc) return rc;
+  *bytes += kCtxHeader - kSegHeader;
+  return TIC_OK;
+}
+
+int tic_rcseg_encode_ctx(const uint8_t* sym, size_t n, uint32_t L, const int64_t* tables, size_t K, size_t ncum,
+                         uint8_t* out, size_t cap, size_t* written) {
+  if (!sym || !out || !written) return rc_fail(TIC_EINVAL, "null argument");
+  *written = 0;
+  size_t bound = 0;
+  int rc = tic_rcseg_bound_ctx(n, L, &bound);
+  if (rc) return rc;
+  std::vector<int64_t> totals;
+  if ((rc = check_ctx_tables(tables, K, ncum, &totals))) return rc;
+  if (cap < bound)
+    return rc_fail(TIC_EINVAL, "output of " + std::to_string(cap) + " bytes is below tic_rcseg_bound_ctx (" + std::to_string(bound) + ")");
+  const size_t S = (n + L - 1) / L, nsym = ncum - 1;
+  memcpy(out, kSegMagic, 4);
+  wr32(out + 4, 2);  // version 2, three zero bytes
+  wr32(out + 8, L);
+  wr32(out + 12, (uint32_t)((uint64_t)n & 0xFFFFFFFFu));
+  wr32(out + 16, (uint32_t)((uint64_t)n >> 32));
+  wr32(out + 20, (uint32_t)K);
+  wr32(out + 24, ctx_tables_crc(tables, K * ncum));
+  uint8_t* lens = out + kCtxHeader;
+  uint8_t* p = lens + 2 * S;
+  for (size_t j = 0; j < S; ++j) {
+    const size_t b = j * L, e = std::min(n, b + L);
+    EncCore<MemSink> c;
+    c.s.p = p;
+    size_t k = b % K;  // the context is a counter that wraps, as on the device
+    for (size_t i = b; i < e; ++i) {
+      const size_t s = sym[i];
+      if (s >= nsym) return rc_fail(TIC_EINVAL, "symbol " + std::to_string(s) + " outside the table (cumFreq too short)");
+      const int64_t* cum = tables + k * ncum;
+      c.symbol((uint64_t)cum[s], (uint64_t)(cum[s + 1] - cum[s]), (uint64_t)totals[k], cum[s + 1] == totals[k]);
+      if (++k == K) k = 0;
+    }
+    c.finish();
+    const size_t len = (size_t)(c.s.p - p);
+    lens[2 * j] = (uint8_t)(len & 0xFF);
+    lens[2 * j + 1] = (uint8_t)(len >> 8);
+    p = c.s.p;
+  }
+  *written = (size_t)(p - out);
+  return TIC_OK;
+}
+
+int tic_rcseg_parse_ctx(const uint8_t* buf, size_t nbytes, uint32_t* L_out, uint64_t* n_out, uint32_t* K_out,
+                        uint32_t* crc_out) {
+  if (!buf) return rc_fail(TIC_EINVAL, "null argument");
+  if (nbytes < kSegHeader) return rc_fail(TIC_EINVAL, "not a segmented stream: shorter than its 20-byte header");
+  if (memcmp(buf, kSegMagic, 4) != 0) return rc_fail(TIC_EINVAL, "not a segmented stream: magic is not \"TICS\"");
+  if (buf[4] != 2)
+    return rc_fail(TIC_EINVAL, "segmented stream version " + std::to_string(buf[4]) + " is not a context stream (version 2)");
+  if (buf[5] || buf[6] || buf[7]) return rc_fail(TIC_EINVAL, "segmented stream: reserved bytes are not zero");
+  if (nbytes < kCtxHeader) return rc_fail(TIC_EINVAL, "context stream: shorter than its 28-byte header");
+  const uint32_t K = rd32(buf + 20);
+  if (K < 1 || K > kCtxMaxK)
+    return rc_fail(TIC_EINVAL, "context stream: context count " + std::to_string(K) + " must be in [1, 65536]");
+  const int rc = parse_framing(buf, nbytes, kCtxHeader, L_out, n_out);
+  if (rc) return rc;
+  if (K_out) *K_out = K;
+  if (crc_out) *crc_out = rd32(buf + 24);
+  return TIC_OK;
+}
+
+int tic_rcseg_decode_ctx(const uint8_t* buf, size_t nbytes, const int64_t* tables, size_t K, size_t ncum,
+                         uint8_t* sym_out, size_t n) {
+  if (!sym_out) return rc_fail(TIC_EINVAL, "null argument");
+  uint32_t L = 0, hK = 0, hcrc = 0;
+  uint64_t hn = 0;
+  int rc = tic_rcseg_parse_ctx(buf, nbytes, &L, &hn, &hK, &hcrc);
+  if (rc) return rc;
+  if (hn != (uint64_t)n)
+    return rc_fail(TIC_EINVAL, "segmented stream holds " + std::to_string(hn) + " symbols, " + std::to_string(n) + " expected");
+  std::vector<int64_t> totals;
+  if ((rc = check_ctx_tables(tables, K, ncum, &totals))) return rc;
+  if ((size_t)hK != K)
+    return rc_fail(TIC_EINVAL, "context stream was coded under " + std::to_string(hK) + " tables, " + std::to_string(K) + " given");
+  if (hcrc != ctx_tables_crc(tables, K * ncum))
+    return rc_fail(TIC_EINVAL, "context stream: the tables' CRC-32C differs from the header's (coded under other tables)");
+  const size_t S = (n + L - 1) / L;
+  const uint8_t* lens = buf + kCtxHeader;
+  const uint8_t* p = lens + 2 * S;
+  for (size_t j = 0; j < S; ++j) {
+    const size_t len = (size_t)lens[2 * j] | (size_t)lens[2 * j + 1] << 8;
+    const size_t b = j * L, e = std::min(n, b + L);
+    DecCore<MemSource> c;
+    c.s.p = p;
+    c.s.end = p + len;
+    c.start();
+    size_t k = b % K;
+    for (size_t i = b; i < e; ++i) {
+      sym_out[i] = (uint8_t)c.symbol(tables + k * ncum, (int64_t)ncum - 1, (uint64_t)totals[k]);
+      if (++k == K) k = 0;
+    }
+    p += len;
+  }
+  return TIC_OK;
+}
+
+}  // extern "C"

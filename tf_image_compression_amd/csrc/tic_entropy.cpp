@@ -1,4 +1,4 @@
-// tic_entropy.cpp — the segmented range-coder stream (include/tic.h, "TICS" version 1) coded on
+// tic_entropy.cpp — the segmented range-coder stream (include/tic.h, "TICS" versions 1 and 2) coded on
 // the device, and its C-ABI entries.
 //
 // The single-stream coder of range_coder.cpp is one latency chain per image.  A segmented stream
@@ -38,6 +38,14 @@
 // the validated table on the host, keyed by the handle; the handle struct belongs to
 // tic_runtime.cpp, which stays as the shipped tuning states were stamped, so tic_destroy is
 // wrapped below to drop that entry with the handle.
+//
+// Version 2 of the container (a periodic context model: K tables, symbol k of a stream under table
+// k mod K; 28-byte header with K and the tables' CRC-32C) runs through the same launches.  The
+// scan, gather and header kernels are templates over the header size; the coder kernels have
+// context variants, ent_encode_ctx_kernel / ent_decode_ctx_kernel, below the version-1 ones, which
+// stay as they were.  K tables do not fit kernel arguments: tic_entropy_set_tables uploads them to
+// a device buffer kept in the same per-handle entry, which the tic_destroy wrapper frees.
+// ent_histogram_ctx_kernel counts symbols per context for estimating such tables.
 //
 // This file closes the one translation unit of the host runtime (it includes tic_msssim.cpp).
 #define tic_destroy tic_destroy_runtime_
@@ -117,6 +125,8 @@ __global__ void __launch_bounds__(64) ent_put_kernel(const EntChunk t, uint32_t 
   if (k == 0 && t.last) seg_base[t.first + t.n] = (unsigned long long)t.seg_base[t.n];
 }
 
+// put / emit_top / the flush below have a second copy in ent_encode_ctx_kernel (this kernel stays
+// as it was measured): a fix to the carry or flush logic goes into both.
 __global__ void __launch_bounds__(64) ent_encode_kernel(const EntModel m, const uint8_t* __restrict__ sym,
                                                         const EntRec* __restrict__ rec,
                                                         const unsigned long long* __restrict__ seg_base, int n_streams,
@@ -223,7 +233,9 @@ __global__ void __launch_bounds__(64) ent_encode_kernel(const EntModel m, const 
   seg_len[g] = bad ? kEntBad : nout;
 }
 
-// Workgroup i: exclusive scan of stream i's segment lengths; its container size.
+// Workgroup i: exclusive scan of stream i's segment lengths; its container size.  HDR: the
+// header's bytes, 20 (version 1) or 28 (version 2), here and in the kernels below.
+template <int HDR>
 __global__ void __launch_bounds__(256) ent_seg_scan_kernel(const EntRec* __restrict__ rec,
                                                            const unsigned long long* __restrict__ seg_base,
                                                            const uint32_t* __restrict__ seg_len,
@@ -251,7 +263,7 @@ __global__ void __launch_bounds__(256) ent_seg_scan_kernel(const EntRec* __restr
   }
   if (bad) s_bad = 1;  // every writer stores the same value
   __syncthreads();
-  if (t == 0) sizes[i] = s_bad ? ~0ull : 20ull + 2ull * S + carry;
+  if (t == 0) sizes[i] = s_bad ? ~0ull : (unsigned long long)HDR + 2ull * S + carry;
 }
 
 // One workgroup: out[i] = sum of in[k], k < i (UINT64_MAX counts as 0); out has n + 1 entries.
@@ -273,6 +285,8 @@ __global__ void __launch_bounds__(256) ent_stream_scan_kernel(const unsigned lon
 }
 
 // Workgroup g: segment g's payload, its length and (first segment) the header to their places.
+// K, crc: the version-2 header's two words (unused by version 1).
+template <int HDR>
 __global__ void __launch_bounds__(256) ent_gather_kernel(const EntRec* __restrict__ rec,
                                                          const unsigned long long* __restrict__ seg_base,
                                                          int n_streams, uint32_t L, const uint8_t* __restrict__ slots,
@@ -280,7 +294,7 @@ __global__ void __launch_bounds__(256) ent_gather_kernel(const EntRec* __restric
                                                          const unsigned long long* __restrict__ seg_off,
                                                          const unsigned long long* __restrict__ sizes,
                                                          const unsigned long long* __restrict__ out_off,
-                                                         uint8_t* __restrict__ out) {
+                                                         uint32_t K, uint32_t crc, uint8_t* __restrict__ out) {
   const unsigned long long g = blockIdx.x;
   const int i = ent_find(seg_base, n_streams, g);
   if (sizes[i] == ~0ull) return;
@@ -288,24 +302,28 @@ __global__ void __launch_bounds__(256) ent_gather_kernel(const EntRec* __restric
   uint8_t* base = out + out_off[i];
   const int t = threadIdx.x;
   const uint32_t len = seg_len[g];
-  if (j == 0 && t < 20) {
+  if (j == 0 && t < HDR) {
     const unsigned long long n = (unsigned long long)rec[i].count;
     uint32_t b;
     if (t < 4) b = (0x53434954u >> (8 * t)) & 0xFFu;  // "TICS"
-    else if (t < 8) b = t == 4 ? 1u : 0u;
+    else if (t < 8) b = t == 4 ? (HDR == 28 ? 2u : 1u) : 0u;
     else if (t < 12) b = (L >> (8 * (t - 8))) & 0xFFu;
-    else b = (uint32_t)(n >> (8 * (t - 12))) & 0xFFu;
+    else if (t < 20) b = (uint32_t)(n >> (8 * (t - 12))) & 0xFFu;
+    else if (t < 24) b = (K >> (8 * (t - 20))) & 0xFFu;
+    else b = (crc >> (8 * (t - 24))) & 0xFFu;
     base[t] = (uint8_t)b;
   }
-  if (t < 2) base[20 + 2 * j + t] = (uint8_t)(len >> (8 * t));
+  if (t < 2) base[HDR + 2 * j + t] = (uint8_t)(len >> (8 * t));
   const uint8_t* src = slots + (size_t)g * ent_stride(L);
-  uint8_t* dst = base + 20 + 2 * S + seg_off[g];
+  uint8_t* dst = base + HDR + 2 * S + seg_off[g];
   for (uint32_t k = t; k < len; k += 256) dst[k] = src[k];
 }
 
-// Lane k: the header of container first + k against the caller's count and size.
+// Lane k: the header of container first + k against the caller's count and size and, version 2,
+// against the K and the CRC of the tables set.
+template <int HDR>
 __global__ void __launch_bounds__(64) ent_dec_header_kernel(const EntChunk t, const uint8_t* __restrict__ blob,
-                                                            EntRec* __restrict__ rec,
+                                                            uint32_t K, uint32_t crc, EntRec* __restrict__ rec,
                                                             unsigned long long* __restrict__ seg_cnt) {
   const int k = threadIdx.x;
   if (k >= t.n) return;
@@ -317,17 +335,26 @@ __global__ void __launch_bounds__(64) ent_dec_header_kernel(const EntChunk t, co
   r.L = 0;
   r.valid = 0;
   unsigned long long S = 0;
-  if (r.in_size >= 20) {
+  if (r.in_size >= HDR) {
     const uint8_t* p = blob + r.in_off;
     uint32_t L = 0;
     unsigned long long n = 0;
     for (int b = 0; b < 4; ++b) L |= (uint32_t)p[8 + b] << (8 * b);
     for (int b = 0; b < 8; ++b) n |= (unsigned long long)p[12 + b] << (8 * b);
-    bool ok = p[0] == 'T' && p[1] == 'I' && p[2] == 'C' && p[3] == 'S' && p[4] == 1 && !p[5] && !p[6] && !p[7];
+    bool ok = p[0] == 'T' && p[1] == 'I' && p[2] == 'C' && p[3] == 'S' && p[4] == (HDR == 28 ? 2 : 1) && !p[5] &&
+              !p[6] && !p[7];
+    if (HDR == 28) {
+      uint32_t hk = 0, hc = 0;
+      for (int b = 0; b < 4; ++b) {
+        hk |= (uint32_t)p[20 + b] << (8 * b);
+        hc |= (uint32_t)p[24 + b] << (8 * b);
+      }
+      ok = ok && hk == K && hc == crc;
+    }
     ok = ok && L >= 4 && L <= kEntMaxL && (L & 3) == 0 && n == (unsigned long long)r.count;
     if (ok) {
       S = (n + L - 1) / L;
-      if (S > (unsigned long long)(r.in_size - 20) / 2) ok = false;
+      if (S > (unsigned long long)(r.in_size - HDR) / 2) ok = false;
     }
     if (ok) {
       r.L = L;
@@ -342,6 +369,7 @@ __global__ void __launch_bounds__(64) ent_dec_header_kernel(const EntChunk t, co
 
 // Workgroup i: the offsets of container i's payloads from its u16 lengths; a container that
 // cannot be decoded (header, or its segments do not fit the scratch) becomes zeros.
+template <int HDR>
 __global__ void __launch_bounds__(256) ent_dec_scan_kernel(const uint8_t* __restrict__ blob, EntRec* __restrict__ rec,
                                                            const unsigned long long* __restrict__ seg_base,
                                                            unsigned long long cap,
@@ -357,8 +385,8 @@ __global__ void __launch_bounds__(256) ent_dec_scan_kernel(const uint8_t* __rest
     if (t == 0) rec[i].valid = 0;
     return;
   }
-  const uint8_t* lens = blob + r.in_off + 20;
-  unsigned long long carry = 20ull + 2ull * S;
+  const uint8_t* lens = blob + r.in_off + HDR;
+  unsigned long long carry = (unsigned long long)HDR + 2ull * S;
   for (unsigned long long j0 = 0; j0 < S; j0 += 256) {
     const unsigned long long j = j0 + t;
     const uint32_t len = j < S ? (uint32_t)lens[2 * j] | (uint32_t)lens[2 * j + 1] << 8 : 0;
@@ -370,7 +398,8 @@ __global__ void __launch_bounds__(256) ent_dec_scan_kernel(const uint8_t* __rest
 }
 
 // One segment per lane, grid-stride.  Dynamic LDS: the cumulative table, then (lut != 0) the
-// value -> symbol bytes.
+// value -> symbol bytes.  The decode step has a second copy in ent_decode_ctx_kernel: a fix to the
+// arithmetic goes into both.
 __global__ void __launch_bounds__(64) ent_decode_kernel(const EntModel m, int lut, const uint8_t* __restrict__ blob,
                                                         const EntRec* __restrict__ rec,
                                                         const unsigned long long* __restrict__ seg_base, int n_streams,
@@ -453,12 +482,269 @@ __global__ void __launch_bounds__(64) ent_decode_kernel(const EntModel m, int lu
   }
 }
 
+// --- version 2: K tables, symbol k of a stream under table k mod K ---
+//
+// The tables lie in a device buffer of the handle (tic_entropy_set_tables), K rows of ncum words:
+// cum[1] .. cum[ncum - 1] (cum[0] is 0 by contract, so it is not stored; the last of them is the
+// row's total), then the row's shift (log2 of the total, or -1).  LDS != 0: every workgroup copies
+// them into dynamic LDS first (K * ncum * 4 <= 64 KiB); else the lanes read them from global
+// memory, where the rows of neighbouring lanes' contexts share cache lines.  A lane carries its
+// context as the word offset of its row, advanced by ncum per symbol and wrapped at K * ncum.
+// The coder arithmetic is that of ent_encode_kernel / ent_decode_kernel, which keep their own
+// copy (the table by value, one total) as they were measured: put / emit_top / the flush and the
+// decoder's renormalisation exist twice, and a fix to either goes into both copies.
+
+template <int LDS>
+__global__ void __launch_bounds__(64) ent_encode_ctx_kernel(const uint32_t* __restrict__ g_tab, uint32_t K,
+                                                            uint32_t ncum, const uint8_t* __restrict__ sym,
+                                                            const EntRec* __restrict__ rec,
+                                                            const unsigned long long* __restrict__ seg_base,
+                                                            int n_streams, uint32_t L, uint8_t* __restrict__ slots,
+                                                            uint32_t* __restrict__ seg_len) {
+  extern __shared__ uint32_t s_dyn[];
+  const uint32_t words = K * ncum;
+  if (LDS) {
+    for (uint32_t k = threadIdx.x; k < words; k += 64) s_dyn[k] = g_tab[k];
+    __syncthreads();
+  }
+  auto tab = [&](uint32_t k) -> uint32_t { return LDS ? s_dyn[k] : g_tab[k]; };
+  const unsigned long long T = seg_base[n_streams];
+  const unsigned long long g = (unsigned long long)blockIdx.x * 64 + threadIdx.x;
+  if (g >= T) return;
+  const int i = ent_find(seg_base, n_streams, g);
+  const unsigned long long j = g - seg_base[i];
+  const long long left = rec[i].count - (long long)(j * L);
+  const uint32_t cnt = left < (long long)L ? (uint32_t)left : L;
+  const uint8_t* src = sym + rec[i].in_off + (long long)(j * L);
+  uint32_t* out = reinterpret_cast<uint32_t*>(slots + (size_t)g * ent_stride(L));
+
+  const uint32_t nsym = ncum - 1;
+  uint32_t row = (uint32_t)((j * L) % K) * ncum;  // every stream starts at context 0
+  unsigned long long low = 0, range = 1ull << 32;
+  int cache = -1;
+  uint32_t pending = 0, nout = 0, acc = 0;
+  bool bad = false;
+
+  auto put = [&](uint32_t b) {
+    acc |= (b & 0xFFu) << (8 * (nout & 3));
+    ++nout;
+    if ((nout & 3) == 0) {
+      out[(nout >> 2) - 1] = acc;
+      acc = 0;
+    }
+  };
+  auto emit_top = [&]() {
+    if (low < 0xFF000000ull || low >= (1ull << 32)) {
+      const uint32_t carry = low >= (1ull << 32) ? 1u : 0u;
+      if (cache >= 0) put((uint32_t)cache + carry);
+      for (; pending; --pending) put(0xFFu + carry);
+      cache = (int)((low >> 24) & 0xFF);
+    } else {
+      ++pending;
+    }
+    low = (low << 8) & 0xFFFFFFFFull;
+  };
+  auto step = [&](uint32_t s) {
+    const uint32_t at = row;
+    row += ncum;
+    if (row == words) row = 0;
+    if (s >= nsym) {
+      bad = true;
+      return;
+    }
+    const uint32_t start = s ? tab(at + s - 1) : 0u, next = tab(at + s), total = tab(at + nsym - 1);
+    const int shift = (int)tab(at + nsym);
+    unsigned long long r;
+    if (shift >= 0) r = range >> shift;
+    else if (range >> 32) r = range / total;
+    else r = (uint32_t)range / total;
+    const unsigned long long sr = (unsigned long long)start * r;
+    low += sr;
+    range = next == total ? range - sr : (unsigned long long)(next - start) * r;
+    while (range < (1ull << 24)) {
+      range <<= 8;
+      emit_top();
+    }
+  };
+
+  uint32_t k = 0;
+  for (; k < cnt && ((uintptr_t)(src + k) & 15) != 0; ++k) step(src[k]);
+  for (; k + 16 <= cnt; k += 16) {
+    const uint4 v = *reinterpret_cast<const uint4*>(src + k);
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      uint32_t x = w[q];
+#pragma unroll 1
+      for (int b = 0; b < 4; ++b) {
+        step(x & 0xFFu);
+        x >>= 8;
+      }
+    }
+  }
+  for (; k < cnt; ++k) step(src[k]);
+
+  // the minimal flush (range_coder.cpp EncCore::finish)
+  int nb = 0;
+  unsigned long long v = low;
+  for (; nb <= 4; ++nb) {
+    if (nb == 4) {
+      v = low;
+    } else {
+      const unsigned long long unit = 1ull << (32 - 8 * nb);
+      v = (low + unit - 1) & ~(unit - 1);
+    }
+    if (v < low + range) break;
+  }
+  low = v;
+  for (int q = 0; q < nb; ++q) emit_top();
+  if (nb > 0) {
+    if (cache >= 0) put((uint32_t)cache);
+    for (; pending; --pending) put(0xFFu);
+  } else if (cache >= 0) {
+    const uint32_t carry = v >= (1ull << 32) ? 1u : 0u;
+    put((uint32_t)cache + carry);
+    for (; pending; --pending) put(0xFFu + carry);
+  }
+  if (nout & 3) out[nout >> 2] = acc;  // the slot is a multiple of 4 bytes
+  seg_len[g] = bad ? kEntBad : nout;
+}
+
+// One segment per lane, grid-stride.  No value -> symbol bytes: with two symbols (ncum == 3, the
+// shipped models) the symbol is one compare with cum[1], otherwise the host's binary search.
+template <int LDS>
+__global__ void __launch_bounds__(64) ent_decode_ctx_kernel(const uint32_t* __restrict__ g_tab, uint32_t K,
+                                                            uint32_t ncum, const uint8_t* __restrict__ blob,
+                                                            const EntRec* __restrict__ rec,
+                                                            const unsigned long long* __restrict__ seg_base,
+                                                            int n_streams,
+                                                            const unsigned long long* __restrict__ seg_off,
+                                                            uint8_t* __restrict__ d_sym) {
+  extern __shared__ uint32_t s_dyn[];
+  const unsigned long long T = seg_base[n_streams];
+  if ((unsigned long long)blockIdx.x * 64 >= T) return;
+  const uint32_t words = K * ncum;
+  if (LDS) {
+    for (uint32_t k = threadIdx.x; k < words; k += 64) s_dyn[k] = g_tab[k];
+    __syncthreads();
+  }
+  auto tab = [&](uint32_t k) -> uint32_t { return LDS ? s_dyn[k] : g_tab[k]; };
+  const uint32_t nsym = ncum - 1;
+  const bool two = ncum == 3;
+
+  for (unsigned long long g = (unsigned long long)blockIdx.x * 64 + threadIdx.x; g < T;
+       g += (unsigned long long)gridDim.x * 64) {
+    const int i = ent_find(seg_base, n_streams, g);
+    const EntRec r = rec[i];
+    if (!r.valid) continue;
+    const unsigned long long j = g - seg_base[i];
+    const long long left = r.count - (long long)(j * r.L);
+    const uint32_t cnt = left < (long long)r.L ? (uint32_t)left : r.L;
+    const uint8_t* cont = blob + r.in_off;
+    const uint32_t len = (uint32_t)cont[28 + 2 * j] | (uint32_t)cont[28 + 2 * j + 1] << 8;
+    // the segment's extent, clamped to the container
+    const unsigned long long size = (unsigned long long)r.in_size;
+    unsigned long long pos = seg_off[g];
+    if (pos > size) pos = size;
+    unsigned long long end = pos + len;
+    if (end > size) end = size;
+    uint8_t* dst = d_sym + r.out_off + (long long)(j * r.L);
+    uint32_t row = (uint32_t)((j * r.L) % K) * ncum;
+
+    auto get = [&]() -> uint32_t { return pos < end ? (uint32_t)cont[pos++] : 0u; };
+    uint32_t code = 0;
+    for (int q = 0; q < 4; ++q) code = (code << 8) | get();
+    unsigned long long range = 1ull << 32;
+    auto dec = [&]() -> uint32_t {
+      const uint32_t at = row;
+      row += ncum;
+      if (row == words) row = 0;
+      const uint32_t total = tab(at + nsym - 1);
+      const int shift = (int)tab(at + nsym);
+      unsigned long long rr;
+      if (shift >= 0) rr = range >> shift;
+      else if (range >> 32) rr = range / total;
+      else rr = (uint32_t)range / total;
+      uint32_t val = (rr >> 32) ? 0u : code / (uint32_t)rr;
+      if (val >= total) val = total - 1;
+      uint32_t s, start, next;
+      if (two) {
+        const uint32_t c1 = tab(at);
+        s = val >= c1 ? 1u : 0u;
+        start = s ? c1 : 0u;
+        next = s ? total : c1;
+      } else {
+        uint32_t lo = 0, hi = nsym - 1;  // last s with cum[s] <= val; cum[mid] is word mid - 1, mid >= 1
+        while (lo < hi) {
+          const uint32_t mid = (lo + hi + 1) >> 1;
+          if (tab(at + mid - 1) <= val) lo = mid;
+          else hi = mid - 1;
+        }
+        s = lo;
+        start = s ? tab(at + s - 1) : 0u;
+        next = tab(at + s);
+      }
+      const unsigned long long sr = (unsigned long long)start * rr;
+      code -= (uint32_t)sr;
+      range = next == total ? range - sr : (unsigned long long)(next - start) * rr;
+      while (range < (1ull << 24)) {
+        range <<= 8;
+        code = (code << 8) | get();
+      }
+      return s;
+    };
+
+    uint32_t k = 0;
+    for (; k < cnt && ((uintptr_t)(dst + k) & 3) != 0; ++k) dst[k] = (uint8_t)dec();
+    for (; k + 4 <= cnt; k += 4) {
+      uint32_t w = 0;
+#pragma unroll 1
+      for (int b = 0; b < 4; ++b) w |= dec() << (8 * b);
+      *reinterpret_cast<uint32_t*>(dst + k) = w;
+    }
+    for (; k < cnt; ++k) dst[k] = (uint8_t)dec();
+  }
+}
+
+// Thread x: one context c (consecutive lanes read consecutive bytes); blockIdx.y strides over the
+// rows of K symbols.  np.histogram semantics as histogram_kernel (v == Q counts in the last bin,
+// larger values in none).  A lane adds a run of equal symbols with one 64-bit atomic: channels
+// are biased, so runs are long.  Integer adds: the sums do not depend on their order.
+__global__ void __launch_bounds__(256) ent_histogram_ctx_kernel(const uint8_t* __restrict__ sym, size_t n, int Q,
+                                                                uint32_t K, unsigned long long* __restrict__ counts) {
+  const uint32_t c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= K) return;
+  unsigned long long* mine = counts + (size_t)c * Q;
+  uint32_t cur = 0, run = 0;
+  for (size_t at = (size_t)blockIdx.y * K + c; at < n; at += (size_t)gridDim.y * K) {
+    uint32_t v = sym[at];
+    if (v == (uint32_t)Q) v = Q - 1;
+    if (v >= (uint32_t)Q) continue;
+    if (v != cur && run) {
+      atomicAdd(&mine[cur], (unsigned long long)run);
+      run = 0;
+    }
+    cur = v;
+    ++run;
+  }
+  if (run) atomicAdd(&mine[cur], (unsigned long long)run);
+}
+
 }  // namespace tic
 
 namespace {
 
+// The version-2 tables of a handle on its device: K rows of ncum words (the layout above
+// ent_encode_ctx_kernel), the CRC the containers carry.
+struct EntTables {
+  uint32_t* d_tab = nullptr;
+  size_t cap_words = 0;
+  uint32_t K = 0, ncum = 0, crc = 0;
+};
 struct EntState {
   tic::EntModel m;
+  bool has_m = false;
+  EntTables t;
 };
 std::mutex g_ent_mu;
 std::map<tic_handle*, EntState> g_ent;
@@ -518,10 +804,31 @@ EntScratch ent_carve(void* d_scratch, int n, long long T) {
 int ent_model(tic_handle* h, tic::EntModel* m) {
   std::lock_guard<std::mutex> lk(g_ent_mu);
   auto it = g_ent.find(h);
-  if (it == g_ent.end()) return fail(TIC_EINVAL, "no entropy table set on this handle (tic_entropy_set_table)");
+  if (it == g_ent.end() || !it->second.has_m)
+    return fail(TIC_EINVAL, "no entropy table set on this handle (tic_entropy_set_table)");
   *m = it->second.m;
   return TIC_OK;
 }
+
+int ent_tables(tic_handle* h, EntTables* t) {
+  std::lock_guard<std::mutex> lk(g_ent_mu);
+  auto it = g_ent.find(h);
+  if (it == g_ent.end() || !it->second.t.d_tab || !it->second.t.K)
+    return fail(TIC_EINVAL, "no context tables set on this handle (tic_entropy_set_tables)");
+  *t = it->second.t;
+  return TIC_OK;
+}
+
+constexpr size_t kEntLdsTables = 64 * 1024;  // tables up to this many bytes are staged in LDS
+
+// Both coders' launches differ between the versions only in the header size, the table's source
+// and the coder kernel: ctx runs version 2.
+int ent_encode(tic_handle* h, const uint8_t* d_sym, const int64_t* sym_offsets, const int64_t* counts, int n_streams,
+               uint32_t L, void* d_scratch, size_t scratch_bytes, uint8_t* d_out, size_t out_cap, uint64_t* d_sizes,
+               bool ctx);
+int ent_decode(tic_handle* h, const uint8_t* d_blob, const int64_t* blob_offsets, const int64_t* blob_sizes,
+               const int64_t* counts, int n_streams, uint8_t* d_sym, const int64_t* sym_offsets, void* d_scratch,
+               size_t scratch_bytes, bool ctx);
 
 }  // namespace
 
@@ -530,9 +837,13 @@ extern "C" {
 void tic_destroy_runtime_(tic_handle* h);
 
 void tic_destroy(tic_handle* h) {
-  {
+  if (h) {
     std::lock_guard<std::mutex> lk(g_ent_mu);
-    g_ent.erase(h);
+    auto it = g_ent.find(h);
+    if (it != g_ent.end()) {
+      if (it->second.t.d_tab && hipSetDevice(h->device) == hipSuccess) (void)hipFree(it->second.t.d_tab);
+      g_ent.erase(it);
+    }
   }
   tic_destroy_runtime_(h);
 }
@@ -555,7 +866,61 @@ int tic_entropy_set_table(tic_handle* h, const int64_t* cum, size_t ncum) {
     for (int s = 0; s <= 24; ++s)
       if ((1u << s) == total) st.m.shift = s;
   std::lock_guard<std::mutex> lk(g_ent_mu);
-  g_ent[h] = st;
+  EntState& cur = g_ent[h];
+  cur.m = st.m;
+  cur.has_m = true;
+  return TIC_OK;
+}
+
+int tic_entropy_set_tables(tic_handle* h, const int64_t* tables, size_t K, size_t ncum) {
+  if (!h) return fail(TIC_EINVAL, "null handle");
+  // the host coder's own check of the tables, and their CRC: one symbol through tic_rcseg_encode_ctx
+  const uint8_t zero = 0;
+  uint8_t out[64];
+  size_t w = 0;
+  const int rc = tic_rcseg_encode_ctx(&zero, 1, 4, tables, K, ncum, out, sizeof(out), &w);
+  if (rc) return fail(rc, "%s", tic_rc_last_error());
+  uint32_t crc = 0;
+  for (int b = 0; b < 4; ++b) crc |= (uint32_t)out[24 + b] << (8 * b);
+  const size_t words = K * ncum;
+  std::vector<uint32_t> host(words);
+  for (size_t k = 0; k < K; ++k) {
+    const int64_t* cum = tables + k * ncum;
+    uint32_t* row = host.data() + k * ncum;
+    for (size_t s = 1; s < ncum; ++s) row[s - 1] = (uint32_t)cum[s];
+    const uint32_t total = (uint32_t)cum[ncum - 1];
+    int shift = -1;
+    if ((total & (total - 1)) == 0)
+      for (int q = 0; q <= 24; ++q)
+        if ((1u << q) == total) shift = q;
+    row[ncum - 1] = (uint32_t)shift;
+  }
+  EntTables t;
+  {
+    std::lock_guard<std::mutex> lk(g_ent_mu);
+    t = g_ent[h].t;
+  }
+  HIP_TRY(hipSetDevice(h->device));
+  touch(h);
+  if (t.cap_words < words) {
+    uint32_t* fresh = nullptr;
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&fresh), words * sizeof(uint32_t)));
+    if (t.d_tab) {  // kernels enqueued earlier may still read the old tables
+      (void)hipStreamSynchronize(h->stream);
+      (void)hipFree(t.d_tab);
+    }
+    t.d_tab = fresh;
+    t.cap_words = words;
+    std::lock_guard<std::mutex> lk(g_ent_mu);
+    g_ent[h].t = EntTables{fresh, words, 0, 0, 0};  // owned from here on; no tables until the copy is done
+  }
+  HIP_TRY(hipMemcpyAsync(t.d_tab, host.data(), words * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));  // `host` is free on return
+  t.K = (uint32_t)K;
+  t.ncum = (uint32_t)ncum;
+  t.crc = crc;
+  std::lock_guard<std::mutex> lk(g_ent_mu);
+  g_ent[h].t = t;
   return TIC_OK;
 }
 
@@ -575,6 +940,57 @@ int tic_entropy_scratch_bytes(const int64_t* counts, int n_streams, uint32_t L, 
 int tic_entropy_encode_device(tic_handle* h, const uint8_t* d_sym, const int64_t* sym_offsets, const int64_t* counts,
                               int n_streams, uint32_t L, void* d_scratch, size_t scratch_bytes, uint8_t* d_out,
                               size_t out_cap, uint64_t* d_sizes) {
+  return ent_encode(h, d_sym, sym_offsets, counts, n_streams, L, d_scratch, scratch_bytes, d_out, out_cap, d_sizes,
+                    false);
+}
+
+int tic_entropy_encode_ctx_device(tic_handle* h, const uint8_t* d_sym, const int64_t* sym_offsets,
+                                  const int64_t* counts, int n_streams, uint32_t L, void* d_scratch,
+                                  size_t scratch_bytes, uint8_t* d_out, size_t out_cap, uint64_t* d_sizes) {
+  return ent_encode(h, d_sym, sym_offsets, counts, n_streams, L, d_scratch, scratch_bytes, d_out, out_cap, d_sizes,
+                    true);
+}
+
+int tic_entropy_decode_device(tic_handle* h, const uint8_t* d_blob, const int64_t* blob_offsets,
+                              const int64_t* blob_sizes, const int64_t* counts, int n_streams, uint8_t* d_sym,
+                              const int64_t* sym_offsets, void* d_scratch, size_t scratch_bytes) {
+  return ent_decode(h, d_blob, blob_offsets, blob_sizes, counts, n_streams, d_sym, sym_offsets, d_scratch,
+                    scratch_bytes, false);
+}
+
+int tic_entropy_decode_ctx_device(tic_handle* h, const uint8_t* d_blob, const int64_t* blob_offsets,
+                                  const int64_t* blob_sizes, const int64_t* counts, int n_streams, uint8_t* d_sym,
+                                  const int64_t* sym_offsets, void* d_scratch, size_t scratch_bytes) {
+  return ent_decode(h, d_blob, blob_offsets, blob_sizes, counts, n_streams, d_sym, sym_offsets, d_scratch,
+                    scratch_bytes, true);
+}
+
+int tic_histogram_ctx_device(tic_handle* h, const uint8_t* d_sym, size_t n, int Q, int K, uint64_t* d_counts) {
+  if (!h) return fail(TIC_EINVAL, "null handle");
+  if (Q < 1 || Q > 256) return fail(TIC_EINVAL, "Q %d must be in [1, 256]", Q);
+  if (K < 1 || K > 65536) return fail(TIC_EINVAL, "context count %d must be in [1, 65536]", K);
+  if (n == 0) return TIC_OK;
+  if (!d_sym || !d_counts) return fail(TIC_EINVAL, "null argument");
+  if (((uintptr_t)d_counts & 7) != 0) return fail(TIC_EINVAL, "d_counts must be 8-byte aligned");
+  HIP_TRY(hipSetDevice(h->device));
+  touch(h);
+  // rows of K symbols over blockIdx.y: enough lanes to fill the device, at most one per row
+  const size_t rows = (n + (size_t)K - 1) / (size_t)K;
+  const unsigned gx = ((unsigned)K + 255) / 256;
+  const size_t want = std::max<size_t>(1, (size_t)h->num_cus * 8 / gx);
+  const unsigned gy = (unsigned)std::min<size_t>(std::min(rows, want), 65535);
+  hipLaunchKernelGGL(tic::ent_histogram_ctx_kernel, dim3(gx, gy), dim3(256), 0, h->stream, d_sym, n, Q, (uint32_t)K,
+                     reinterpret_cast<unsigned long long*>(d_counts));
+  return check_launch();
+}
+
+}  // extern "C"
+
+namespace {
+
+int ent_encode(tic_handle* h, const uint8_t* d_sym, const int64_t* sym_offsets, const int64_t* counts, int n_streams,
+               uint32_t L, void* d_scratch, size_t scratch_bytes, uint8_t* d_out, size_t out_cap, uint64_t* d_sizes,
+               bool ctx) {
   if (!h) return fail(TIC_EINVAL, "null handle");
   if (n_streams < 0) return fail(TIC_EINVAL, "n_streams %d is negative", n_streams);
   if (n_streams == 0) return TIC_OK;
@@ -588,10 +1004,11 @@ int tic_entropy_encode_device(tic_handle* h, const uint8_t* d_sym, const int64_t
   for (int i = 0; i < n_streams; ++i) {
     if (sym_offsets[i] < 0) return fail(TIC_EINVAL, "stream %d: negative offset %lld", i, (long long)sym_offsets[i]);
     const size_t S = ((size_t)counts[i] + L - 1) / L;
-    bound += 20 + 2 * S + 3 * (size_t)counts[i] + 4 * S;
+    bound += (ctx ? 28 : 20) + 2 * S + 3 * (size_t)counts[i] + 4 * S;
   }
   tic::EntModel m;
-  int rc = ent_model(h, &m);
+  EntTables tb;
+  int rc = ctx ? ent_tables(h, &tb) : ent_model(h, &m);
   if (rc) return rc;
   if (((uintptr_t)d_scratch & 15) != 0 || ((uintptr_t)d_sizes & 7) != 0)
     return fail(TIC_EINVAL, "d_scratch must be 16-byte and d_sizes 8-byte aligned");
@@ -599,9 +1016,15 @@ int tic_entropy_encode_device(tic_handle* h, const uint8_t* d_sym, const int64_t
   if (scratch_bytes < need)
     return fail(TIC_EINVAL, "scratch of %zu bytes is too small (tic_entropy_scratch_bytes: %zu)", scratch_bytes, need);
   if (out_cap < bound)
-    return fail(TIC_EINVAL, "out_cap %zu is below the sum of tic_rcseg_bound (%zu)", out_cap, bound);
+    return fail(TIC_EINVAL, "out_cap %zu is below the sum of tic_rcseg_bound%s (%zu)", out_cap, ctx ? "_ctx" : "",
+                bound);
+  const size_t tab_bytes = ctx ? (size_t)tb.K * tb.ncum * sizeof(uint32_t) : 0;
+  const bool in_lds = tab_bytes <= kEntLdsTables;
 
   HIP_TRY(hipSetDevice(h->device));
+  if (ctx && in_lds && tab_bytes > 48 * 1024)
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(tic::ent_encode_ctx_kernel<1>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)tab_bytes));
   const EntScratch s = ent_carve(d_scratch, n_streams, T);
   long long segs = 0;
   for (int f = 0; f < n_streams; f += tic::kEntStreams) {
@@ -622,27 +1045,45 @@ int tic_entropy_encode_device(tic_handle* h, const uint8_t* d_sym, const int64_t
     if ((rc = check_launch())) return rc;
   }
   const unsigned wgs = (unsigned)((T + 63) / 64);
-  hipLaunchKernelGGL(tic::ent_encode_kernel, dim3(wgs), dim3(64), 0, h->stream, m, d_sym, (const tic::EntRec*)s.rec,
-                     (const unsigned long long*)s.seg_base, n_streams, L, s.slots, s.seg_len);
+  const tic::EntRec* rec = s.rec;
+  const unsigned long long* seg_base = s.seg_base;
+  if (!ctx)
+    hipLaunchKernelGGL(tic::ent_encode_kernel, dim3(wgs), dim3(64), 0, h->stream, m, d_sym, rec, seg_base, n_streams,
+                       L, s.slots, s.seg_len);
+  else if (in_lds)
+    hipLaunchKernelGGL(tic::ent_encode_ctx_kernel<1>, dim3(wgs), dim3(64), tab_bytes, h->stream,
+                       (const uint32_t*)tb.d_tab, tb.K, tb.ncum, d_sym, rec, seg_base, n_streams, L, s.slots,
+                       s.seg_len);
+  else
+    hipLaunchKernelGGL(tic::ent_encode_ctx_kernel<0>, dim3(wgs), dim3(64), 0, h->stream, (const uint32_t*)tb.d_tab,
+                       tb.K, tb.ncum, d_sym, rec, seg_base, n_streams, L, s.slots, s.seg_len);
   if ((rc = check_launch())) return rc;
   unsigned long long* sizes = reinterpret_cast<unsigned long long*>(d_sizes);
-  hipLaunchKernelGGL(tic::ent_seg_scan_kernel, dim3((unsigned)n_streams), dim3(256), 0, h->stream,
-                     (const tic::EntRec*)s.rec, (const unsigned long long*)s.seg_base, (const uint32_t*)s.seg_len,
-                     s.seg_off, sizes);
+  const uint32_t* seg_len = s.seg_len;
+  if (ctx)
+    hipLaunchKernelGGL(tic::ent_seg_scan_kernel<28>, dim3((unsigned)n_streams), dim3(256), 0, h->stream, rec, seg_base,
+                       seg_len, s.seg_off, sizes);
+  else
+    hipLaunchKernelGGL(tic::ent_seg_scan_kernel<20>, dim3((unsigned)n_streams), dim3(256), 0, h->stream, rec, seg_base,
+                       seg_len, s.seg_off, sizes);
   if ((rc = check_launch())) return rc;
   hipLaunchKernelGGL(tic::ent_stream_scan_kernel, dim3(1), dim3(256), 0, h->stream, (const unsigned long long*)sizes,
                      n_streams, s.aux);
   if ((rc = check_launch())) return rc;
-  hipLaunchKernelGGL(tic::ent_gather_kernel, dim3((unsigned)T), dim3(256), 0, h->stream, (const tic::EntRec*)s.rec,
-                     (const unsigned long long*)s.seg_base, n_streams, L, (const uint8_t*)s.slots,
-                     (const uint32_t*)s.seg_len, (const unsigned long long*)s.seg_off,
-                     (const unsigned long long*)sizes, (const unsigned long long*)s.aux, d_out);
+  const uint8_t* slots = s.slots;
+  const unsigned long long *seg_off = s.seg_off, *csizes = sizes, *out_off = s.aux;
+  if (ctx)
+    hipLaunchKernelGGL(tic::ent_gather_kernel<28>, dim3((unsigned)T), dim3(256), 0, h->stream, rec, seg_base,
+                       n_streams, L, slots, seg_len, seg_off, csizes, out_off, tb.K, tb.crc, d_out);
+  else
+    hipLaunchKernelGGL(tic::ent_gather_kernel<20>, dim3((unsigned)T), dim3(256), 0, h->stream, rec, seg_base,
+                       n_streams, L, slots, seg_len, seg_off, csizes, out_off, 0u, 0u, d_out);
   return check_launch();
 }
 
-int tic_entropy_decode_device(tic_handle* h, const uint8_t* d_blob, const int64_t* blob_offsets,
-                              const int64_t* blob_sizes, const int64_t* counts, int n_streams, uint8_t* d_sym,
-                              const int64_t* sym_offsets, void* d_scratch, size_t scratch_bytes) {
+int ent_decode(tic_handle* h, const uint8_t* d_blob, const int64_t* blob_offsets, const int64_t* blob_sizes,
+               const int64_t* counts, int n_streams, uint8_t* d_sym, const int64_t* sym_offsets, void* d_scratch,
+               size_t scratch_bytes, bool ctx) {
   if (!h) return fail(TIC_EINVAL, "null handle");
   if (n_streams < 0) return fail(TIC_EINVAL, "n_streams %d is negative", n_streams);
   if (n_streams == 0) return TIC_OK;
@@ -655,7 +1096,8 @@ int tic_entropy_decode_device(tic_handle* h, const uint8_t* d_blob, const int64_
     if (blob_offsets[i] < 0 || blob_sizes[i] < 0 || sym_offsets[i] < 0)
       return fail(TIC_EINVAL, "stream %d: negative offset or size", i);
   tic::EntModel m;
-  int rc = ent_model(h, &m);
+  EntTables tb;
+  int rc = ctx ? ent_tables(h, &tb) : ent_model(h, &m);
   if (rc) return rc;
   if (((uintptr_t)d_scratch & 15) != 0) return fail(TIC_EINVAL, "d_scratch must be 16-byte aligned");
   const size_t fixed = ent_fixed(n_streams);
@@ -664,12 +1106,15 @@ int tic_entropy_decode_device(tic_handle* h, const uint8_t* d_blob, const int64_
   // segments the scratch has room for: the containers' own L decides how many there are
   const unsigned long long cap = std::min<unsigned long long>((scratch_bytes - fixed) / 8, INT_MAX);
 
-  const uint32_t total = m.cum[m.nsym];
-  const int lut = total <= tic::kEntLutMax;
-  const size_t lds = 260 * sizeof(uint32_t) + (lut ? ((size_t)total + 3) / 4 * 4 : 0);
+  const uint32_t total = ctx ? 0 : m.cum[m.nsym];
+  const int lut = !ctx && total <= tic::kEntLutMax;
+  const size_t tab_bytes = ctx ? (size_t)tb.K * tb.ncum * sizeof(uint32_t) : 0;
+  const bool in_lds = tab_bytes <= kEntLdsTables;
+  const size_t lds = ctx ? (in_lds ? tab_bytes : 0) : 260 * sizeof(uint32_t) + (lut ? ((size_t)total + 3) / 4 * 4 : 0);
   HIP_TRY(hipSetDevice(h->device));
   if (lds > 48 * 1024)
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(tic::ent_decode_kernel),
+    HIP_TRY(hipFuncSetAttribute(ctx ? reinterpret_cast<const void*>(tic::ent_decode_ctx_kernel<1>)
+                                    : reinterpret_cast<const void*>(tic::ent_decode_kernel),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   const EntScratch s = ent_carve(d_scratch, n_streams, 0);
   for (int f = 0; f < n_streams; f += tic::kEntStreams) {
@@ -684,20 +1129,38 @@ int tic_entropy_decode_device(tic_handle* h, const uint8_t* d_blob, const int64_
       t.out_off[k] = sym_offsets[f + k];
     }
     touch(h);
-    hipLaunchKernelGGL(tic::ent_dec_header_kernel, dim3(1), dim3(64), 0, h->stream, t, d_blob, s.rec, s.aux);
+    if (ctx)
+      hipLaunchKernelGGL(tic::ent_dec_header_kernel<28>, dim3(1), dim3(64), 0, h->stream, t, d_blob, tb.K, tb.crc,
+                         s.rec, s.aux);
+    else
+      hipLaunchKernelGGL(tic::ent_dec_header_kernel<20>, dim3(1), dim3(64), 0, h->stream, t, d_blob, 0u, 0u, s.rec,
+                         s.aux);
     if ((rc = check_launch())) return rc;
   }
   hipLaunchKernelGGL(tic::ent_stream_scan_kernel, dim3(1), dim3(256), 0, h->stream, (const unsigned long long*)s.aux,
                      n_streams, s.seg_base);
   if ((rc = check_launch())) return rc;
-  hipLaunchKernelGGL(tic::ent_dec_scan_kernel, dim3((unsigned)n_streams), dim3(256), 0, h->stream, d_blob, s.rec,
-                     (const unsigned long long*)s.seg_base, cap, s.seg_off, d_sym);
+  const unsigned long long* seg_base = s.seg_base;
+  if (ctx)
+    hipLaunchKernelGGL(tic::ent_dec_scan_kernel<28>, dim3((unsigned)n_streams), dim3(256), 0, h->stream, d_blob, s.rec,
+                       seg_base, cap, s.seg_off, d_sym);
+  else
+    hipLaunchKernelGGL(tic::ent_dec_scan_kernel<20>, dim3((unsigned)n_streams), dim3(256), 0, h->stream, d_blob, s.rec,
+                       seg_base, cap, s.seg_off, d_sym);
   if ((rc = check_launch())) return rc;
   const unsigned wgs = (unsigned)std::min<unsigned long long>((cap + 63) / 64, 1u << 16);
-  hipLaunchKernelGGL(tic::ent_decode_kernel, dim3(wgs), dim3(64), lds, h->stream, m, lut, d_blob,
-                     (const tic::EntRec*)s.rec, (const unsigned long long*)s.seg_base, n_streams,
-                     (const unsigned long long*)s.seg_off, d_sym);
+  const tic::EntRec* rec = s.rec;
+  const unsigned long long* seg_off = s.seg_off;
+  if (!ctx)
+    hipLaunchKernelGGL(tic::ent_decode_kernel, dim3(wgs), dim3(64), lds, h->stream, m, lut, d_blob, rec, seg_base,
+                       n_streams, seg_off, d_sym);
+  else if (in_lds)
+    hipLaunchKernelGGL(tic::ent_decode_ctx_kernel<1>, dim3(wgs), dim3(64), lds, h->stream, (const uint32_t*)tb.d_tab,
+                       tb.K, tb.ncum, d_blob, rec, seg_base, n_streams, seg_off, d_sym);
+  else
+    hipLaunchKernelGGL(tic::ent_decode_ctx_kernel<0>, dim3(wgs), dim3(64), 0, h->stream, (const uint32_t*)tb.d_tab,
+                       tb.K, tb.ncum, d_blob, rec, seg_base, n_streams, seg_off, d_sym);
   return check_launch();
 }
 
-}  // extern "C"
+}  // namespace

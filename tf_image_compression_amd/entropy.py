@@ -1,4 +1,4 @@
-"""Segmented range-coder streams ("TICS" version 1, include/tic.h), host side.
+"""Segmented range-coder streams ("TICS" versions 1 and 2, include/tic.h), host side.
 
 A container cuts a symbol sequence into segments of ``L`` symbols, each an independent stream of
 the range coder in csrc/range_coder.cpp (byte for byte what ``RangeEncoder`` writes for the
@@ -8,6 +8,11 @@ functions here are its reference and read or write a container without a GPU.
 
 Symbols are bytes; the table is a ``range_coder`` cumulative table with at most 256 symbols and
 no zero frequency.  Errors are mapped as ``range_coder._raise`` maps them.
+
+A 2-D table ``[K, ncum]`` selects the periodic context model of version 2: symbol ``k`` of the
+stream is coded under row ``k mod K`` (``K`` = the code's channel count: one table per channel;
+``K`` = the symbols of a patch: one per code position).  ``pack``, ``unpack`` and ``bound`` take
+either kind of table; ``parse`` reads version 1 only and ``parse_ctx`` version 2 only.
 """
 from __future__ import annotations
 
@@ -20,6 +25,7 @@ from .range_coder import _raise, _table
 
 MAGIC = b"TICS"
 HEADER_BYTES = 20
+HEADER_BYTES_CTX = 28
 DEFAULT_SEGMENT = 2048  # faster than 4096 end to end, under 1 % bytes over the single stream
 
 
@@ -45,24 +51,61 @@ def is_container(buf) -> bool:
     return bytes(buf[:4]) == MAGIC
 
 
-def bound(n: int, segment: int = DEFAULT_SEGMENT) -> int:
-    """Worst-case container size for ``n`` symbols."""
+def container_version(buf) -> int:
+    """The version byte of a container (no validation); ValueError without the magic."""
+    if not is_container(buf) or len(buf) < 5:
+        raise ValueError("not a segmented stream: magic is not \"TICS\"")
+    return int(bytes(buf[4:5])[0])
+
+
+def is_ctx_table(cum_freq) -> bool:
+    """True for a 2-D ``[K, ncum]`` table (version 2), False for a 1-D one (version 1)."""
+    try:
+        return len(cum_freq) > 0 and np.ndim(cum_freq[0]) > 0
+    except TypeError:
+        return False
+
+
+def ctx_tables(tables) -> np.ndarray:
+    """``[K, ncum]`` cumulative tables as a C-contiguous int64 array (``range_coder`` contract
+    per entry: integers below 2^32)."""
+    rows = [_table(row) for row in tables]
+    if not rows or len({r.size for r in rows}) != 1:
+        raise ValueError("context tables need at least one row and one common length")
+    return np.ascontiguousarray(np.stack(rows))
+
+
+def tables_crc(tables) -> int:
+    """The CRC-32C a version-2 header carries: of the ``K * ncum`` entries as little-endian
+    int64, row-major."""
+    data = ctx_tables(tables).astype("<i8").tobytes()
+    return int(lib().tic_crc32c(data, len(data), 0))
+
+
+def bound(n: int, segment: int = DEFAULT_SEGMENT, cum_freq=None) -> int:
+    """Worst-case container size for ``n`` symbols (version 2 when ``cum_freq`` is 2-D)."""
     out = C.c_size_t()
-    rc = lib().tic_rcseg_bound(int(n), int(segment), C.byref(out))
+    fn = lib().tic_rcseg_bound_ctx if cum_freq is not None and is_ctx_table(cum_freq) else lib().tic_rcseg_bound
+    rc = fn(int(n), int(segment), C.byref(out))
     if rc:
         _raise(rc, "entropy.bound")
     return int(out.value)
 
 
 def pack(symbols, cum_freq, segment: int = DEFAULT_SEGMENT) -> bytes:
-    """The container of ``symbols`` (flattened in C order)."""
-    table = _table(cum_freq)
+    """The container of ``symbols`` (flattened in C order); version 2 under a 2-D table."""
+    ctx = is_ctx_table(cum_freq)
+    table = ctx_tables(cum_freq) if ctx else _table(cum_freq)
     sym = _symbols(symbols)
-    cap = bound(sym.size, segment)
+    cap = bound(sym.size, segment, cum_freq)
     out = np.empty(cap, np.uint8)
     written = C.c_size_t()
-    rc = lib().tic_rcseg_encode(_u8(sym), sym.size, int(segment), _i64(table), table.size, _u8(out), cap,
-                                C.byref(written))
+    if ctx:
+        rc = lib().tic_rcseg_encode_ctx(_u8(sym), sym.size, int(segment), _i64(table), table.shape[0],
+                                        table.shape[1], _u8(out), cap, C.byref(written))
+    else:
+        rc = lib().tic_rcseg_encode(_u8(sym), sym.size, int(segment), _i64(table), table.size, _u8(out), cap,
+                                    C.byref(written))
     if rc:
         _raise(rc, "entropy.pack")
     return out[:written.value].tobytes()
@@ -78,14 +121,31 @@ def parse(buf) -> tuple[int, int]:
     return int(L.value), int(n.value)
 
 
+def parse_ctx(buf) -> tuple[int, int, int, int]:
+    """Validate a version-2 container; ``(L, n, K, crc)``."""
+    a = np.frombuffer(bytes(buf), np.uint8)
+    L, n, K, crc = C.c_uint32(), C.c_uint64(), C.c_uint32(), C.c_uint32()
+    rc = lib().tic_rcseg_parse_ctx(_u8(a) if a.size else None, a.size, C.byref(L), C.byref(n), C.byref(K),
+                                   C.byref(crc))
+    if rc:
+        _raise(rc, "entropy.parse_ctx")
+    return int(L.value), int(n.value), int(K.value), int(crc.value)
+
+
 def unpack(buf, cum_freq, n: int | None = None) -> np.ndarray:
-    """The symbols of a container (uint8); ``n``, when given, must be the header's count."""
-    table = _table(cum_freq)
+    """The symbols of a container (uint8); ``n``, when given, must be the header's count.  A 2-D
+    table reads version 2 and must be the one the container was packed under (its K and CRC)."""
+    ctx = is_ctx_table(cum_freq)
+    table = ctx_tables(cum_freq) if ctx else _table(cum_freq)
     a = np.frombuffer(bytes(buf), np.uint8)
     if n is None:
-        _, n = parse(a)
+        n = parse_ctx(a)[1] if ctx else parse(a)[1]
     out = np.empty(int(n), np.uint8)
-    rc = lib().tic_rcseg_decode(_u8(a) if a.size else None, a.size, _i64(table), table.size, _u8(out), int(n))
+    if ctx:
+        rc = lib().tic_rcseg_decode_ctx(_u8(a) if a.size else None, a.size, _i64(table), table.shape[0],
+                                        table.shape[1], _u8(out), int(n))
+    else:
+        rc = lib().tic_rcseg_decode(_u8(a) if a.size else None, a.size, _i64(table), table.size, _u8(out), int(n))
     if rc:
         _raise(rc, "entropy.unpack")
     return out

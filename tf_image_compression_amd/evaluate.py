@@ -21,6 +21,8 @@ reference's evaluate.py) follows Wang et al. 2003 with the choices of
 * ``msssim(a, b, codec)``           two host arrays.
 * ``estimated_bits(counts, cum_freq)``  the ideal code length of a symbol histogram under
   the range coder's table (encode.py:77-97), known before any file is written.
+* ``estimated_bits_ctx(counts, tables)``  the same under the ``K`` tables of a periodic context
+  model (entropy.py), from the per-context histogram ``counts[K, Q]``.
 
 As elsewhere there is no CPU fallback for the device parts.
 """
@@ -162,3 +164,18 @@ def estimated_bits(counts, cum_freq) -> float:
     if np.any(freq[used] <= 0):
         raise ValueError("a symbol with a count has zero frequency in the table")
     return float(-np.sum(c[used] * np.log2(freq[used] / cf[-1])))
+
+
+def estimated_bits_ctx(counts, tables) -> float:
+    """sum over the contexts k of estimated_bits(counts[k], tables[k]): ``counts[K, Q]`` is the
+    per-context histogram (tic_histogram_ctx_device), ``tables[K, Q + 1]`` the cumulative tables."""
+    c = np.asarray(counts, np.float64)
+    cf = np.asarray(tables, np.float64)
+    if c.ndim != 2 or cf.ndim != 2 or cf.shape != (c.shape[0], c.shape[1] + 1):
+        raise ValueError(f"counts {c.shape} do not fit context tables {cf.shape}")
+    freq = np.diff(cf, axis=1)
+    used = c > 0
+    if np.any(freq[used] <= 0):
+        raise ValueError("a symbol with a count has zero frequency in its context's table")
+    p = freq / cf[:, -1:]
+    return float(-np.sum(c[used] * np.log2(p[used])))

@@ -318,21 +318,28 @@ class ImageCodec:
     # The entropy coder on the device (tic_entropy.cpp): the symbols of a group never visit the
     # host, every image becomes one "TICS" container (entropy.py), all of them in one coder call.
     def _entropy_encode(self, d_sym: DeviceBuffer, counts, cum_freq, segment: int):
-        """Symbols of consecutive streams in ``d_sym`` -> (d_blob, d_sizes), nothing downloaded."""
+        """Symbols of consecutive streams in ``d_sym`` -> (d_blob, d_sizes), nothing downloaded.
+        A 2-D ``cum_freq`` ([K, ncum], entropy.py) takes the context coder: version-2 containers."""
+        from . import entropy
         c = self.codec
-        c.entropy_set_table(cum_freq)
+        ctx = entropy.is_ctx_table(cum_freq)
+        if ctx:
+            c.entropy_set_tables(cum_freq)
+        else:
+            c.entropy_set_table(cum_freq)
         offs = np.concatenate([[0], np.cumsum(counts)[:-1]]).astype(np.int64)
         d_scr = self._buf("entropy_scratch", c.entropy_scratch_bytes(counts, segment))
-        from . import entropy
-        d_blob = self._buf("entropy_blob", sum(entropy.bound(n, segment) for n in counts))
+        d_blob = self._buf("entropy_blob", sum(entropy.bound(n, segment, cum_freq) for n in counts))
         d_sizes = self._buf("entropy_sizes", 8 * len(counts))
-        c.entropy_encode_device(d_sym, offs, counts, segment, d_scr, d_blob, d_sizes)
+        encode = c.entropy_encode_ctx_device if ctx else c.entropy_encode_device
+        encode(d_sym, offs, counts, segment, d_scr, d_blob, d_sizes)
         return d_blob, d_sizes
 
     def encode_images_to_streams(self, images, cum_freq, segment: int = 2048) -> list[bytes]:
         """[uint8 [H_i, W_i, 3]] -> one segmented-stream container per image (entropy.unpack gives
         ``encode_images``' symbols back): one upload, ``encode_images_device``, one coder call over
-        all images, one download of the sizes and one of the containers."""
+        all images, one download of the sizes and one of the containers.  A 2-D ``cum_freq``
+        ([K, ncum]) codes symbol k of an image under row k mod K and writes version-2 containers."""
         imgs = [np.ascontiguousarray(im) for im in images]
         for im in imgs:
             if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3 or im.size == 0:
@@ -359,8 +366,13 @@ class ImageCodec:
     def decode_streams_to_images(self, streams, sizes, cum_freq, post_filter: bool = True) -> list[np.ndarray]:
         """[container], [(H_i, W_i)] -> [uint8 [H_i, W_i, 3]]: every container is validated on the
         host (entropy.parse) and its symbol count checked against the image size and the code
-        shape; then one upload, one decoder call for all of them and ``decode_images_device``."""
+        shape; then one upload, one decoder call for all of them and ``decode_images_device``.  A 2-D
+        ``cum_freq`` reads version-2 containers, which must have been coded under these tables."""
         from . import entropy
+        ctx = entropy.is_ctx_table(cum_freq)
+        if ctx:
+            tables = entropy.ctx_tables(cum_freq)
+            crc = entropy.tables_crc(tables)
         sizes = [(int(H), int(W)) for H, W in sizes]
         if len(streams) != len(sizes):
             raise ValueError(f"{len(streams)} streams for {len(sizes)} image sizes")
@@ -372,7 +384,13 @@ class ImageCodec:
         for i, (buf, (H, W)) in enumerate(zip(streams, sizes)):
             if H <= 0 or W <= 0:
                 raise ValueError(f"image size {H}x{W} must be positive")
-            L, n = entropy.parse(buf)
+            if ctx:
+                L, n, K, hcrc = entropy.parse_ctx(buf)
+                if K != tables.shape[0] or hcrc != crc:
+                    raise ValueError(f"stream {i} was coded under other context tables (K {K}, CRC {hcrc:#010x}; "
+                                     f"given K {tables.shape[0]}, CRC {crc:#010x})")
+            else:
+                L, n = entropy.parse(buf)
             want = self.num_patches(H, W) * code
             if n != want:
                 raise ValueError(f"stream {i} holds {n} symbols, a {H}x{W} image has {want}")
@@ -382,12 +400,16 @@ class ImageCodec:
         bsizes = [len(b) for b in streams]
         boffs = np.concatenate([[0], np.cumsum(bsizes)[:-1]]).astype(np.int64)
         soffs = np.concatenate([[0], np.cumsum(counts)[:-1]]).astype(np.int64)
-        c.entropy_set_table(cum_freq)
+        if ctx:
+            c.entropy_set_tables(tables)
+        else:
+            c.entropy_set_table(cum_freq)
         d_blob = self._buf("entropy_blob", blob.size)
         d_blob.upload(blob)
         d_scr = self._buf("entropy_scratch", c.entropy_scratch_bytes(counts, min_L))
         d_sym = self._buf("symbols", sum(counts))
-        c.entropy_decode_device(d_blob, boffs, bsizes, counts, d_sym, soffs, d_scr)
+        decode = c.entropy_decode_ctx_device if ctx else c.entropy_decode_device
+        decode(d_blob, boffs, bsizes, counts, d_sym, soffs, d_scr)
         offsets, total = self.packed_offsets(sizes)
         d_out = self._buf("image_out", total)
         self.decode_images_device(d_sym, offsets, sizes, d_out, post_filter)
@@ -409,9 +431,13 @@ class ImageCodec:
         without one).  With ``entropy_segment`` and ``cum_freq`` every result also has
         ``coded_bytes``: the size of the image's segmented-stream container at that segment length,
         from one entropy_encode_device call over the symbols on the device (the real rate beside
-        the estimate).  Images start at 4-byte boundaries of the arena (the alignment
-        tic_sse_u8_device asks for)."""
+        the estimate).  Under a 2-D ``cum_freq`` ([K, Q + 1] context tables, entropy.py)
+        ``est_bits`` is evaluate.estimated_bits_ctx of the image's per-context histogram
+        (tic_histogram_ctx_device) and ``coded_bytes`` the size of its version-2 container.  Images
+        start at 4-byte boundaries of the arena (the alignment tic_sse_u8_device asks for)."""
+        from . import entropy
         from . import evaluate as ev
+        tables = entropy.ctx_tables(cum_freq) if cum_freq is not None and entropy.is_ctx_table(cum_freq) else None
         imgs = [np.ascontiguousarray(im) for im in images]
         for im in imgs:
             if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3 or im.size == 0:
@@ -455,6 +481,17 @@ class ImageCodec:
             bsizes = [sizes[i] for i in big]
             d_scr = self._buf("msssim_scratch", c.msssim_scratch_bytes(bsizes))
             c.msssim_images_device(d_img, d_out, [offsets[i] for i in big], bsizes, d_scr, d_res.view(n * rec))
+        ctx_counts = None
+        if tables is not None:
+            K = tables.shape[0]
+            if tables.shape[1] != Q + 1:
+                raise ValueError(f"context tables of {tables.shape[1] - 1} symbols for a quantiser of {Q}")
+            d_ctx = self._buf("eval_ctx_counts", n * K * Q * 8)
+            c.memset_device(d_ctx, 0, n * K * Q * 8)
+            for i in range(n):
+                c.histogram_ctx_device(d_sym.view(int(pbase[i]) * code), counts[i] * code, Q, K,
+                                       d_ctx.view(i * K * Q * 8))
+            ctx_counts = d_ctx.download((n, K, Q), np.uint64)
         raw = d_res.download((n * rec + len(big) * 240,), np.uint8)
         ints = raw[:n * rec].view(np.uint64).reshape(n, 1 + Q)
         sums = raw[n * rec:].view(np.float64).reshape(len(big), 5, 3, 2)
@@ -468,9 +505,14 @@ class ImageCodec:
             cnt = ints[i, 1:].copy()
             with np.errstate(divide="ignore"):
                 psnr = float(ev.mse2psnr(np.float64(sse) / (H * W * 3)))
+            if cum_freq is None:
+                est = None
+            elif tables is not None:
+                est = ev.estimated_bits_ctx(ctx_counts[i], tables)
+            else:
+                est = ev.estimated_bits(cnt, cum_freq)
             out.append({"sse": sse, "psnr": psnr, "msssim": ms.get(i, float("nan")), "counts": cnt,
-                        "n_symbols": counts[i] * code,
-                        "est_bits": None if cum_freq is None else ev.estimated_bits(cnt, cum_freq)})
+                        "n_symbols": counts[i] * code, "est_bits": est})
             if coded is not None:
                 out[-1]["coded_bytes"] = int(coded[i])
         return out

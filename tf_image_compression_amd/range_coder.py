@@ -164,3 +164,27 @@ def symbol_table(prob, resolution=4096):
     prob_to_cum_freq(..., resolution)."""
     modified_freq = np.asarray(prob, np.float64) * resolution + 1
     return prob_to_cum_freq(modified_freq / np.sum(modified_freq), resolution=resolution)
+
+
+def dist_is_ctx(path) -> bool:
+    """True when the distribution file at ``path`` holds a 2-D ``[K, Q]`` array (the per-context
+    probabilities get_encoded_distribution.py --context writes); False for the 1-D table or a
+    missing file."""
+    if not os.path.exists(path):
+        return False
+    return np.load(path, mmap_mode="r", allow_pickle=False).ndim == 2
+
+
+def dist_table(prob, resolution=4096):
+    """The coder's table(s) of a distribution array: ``symbol_table`` of a 1-D one,
+    ``symbol_tables`` of a 2-D one."""
+    return symbol_tables(prob, resolution) if np.ndim(prob) == 2 else symbol_table(prob, resolution)
+
+
+def symbol_tables(prob, resolution=4096):
+    """``symbol_table`` of every row of ``prob[K, Q]``: the ``[K, Q + 1]`` tables of a periodic
+    context model (entropy.py, "TICS" version 2), as an int64 array."""
+    p = np.asarray(prob, np.float64)
+    if p.ndim != 2 or p.shape[0] == 0:
+        raise ValueError(f"context probabilities must be [K, Q], got shape {p.shape}")
+    return np.array([symbol_table(row, resolution=resolution) for row in p], dtype=np.int64)
