@@ -64,7 +64,16 @@ $(RCSEG_CTX_BIN): tests/native/rcseg_ctx_fuzz.cpp $(CSRC)/range_coder.cpp $(CSRC
 	g++ -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=all \
 	    -Iinclude -o $@ tests/native/rcseg_ctx_fuzz.cpp $(CSRC)/range_coder.cpp $(CSRC)/host_util.cpp
 
+# The version-3 (causal-neighbour) container entries (tic_rcseg_*_nbr), the same way.
+RCSEG_NBR_BIN := $(BUILD)/rcseg_nbr_fuzz_asan
+asan-rcseg-nbr: $(RCSEG_NBR_BIN)
+	$(RCSEG_NBR_BIN) $(BUILD)
+
+$(RCSEG_NBR_BIN): tests/native/rcseg_nbr_fuzz.cpp $(CSRC)/range_coder.cpp $(CSRC)/host_util.cpp include/tic.h | $(BUILD)
+	g++ -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=all \
+	    -Iinclude -o $@ tests/native/rcseg_nbr_fuzz.cpp $(CSRC)/range_coder.cpp $(CSRC)/host_util.cpp
+
 clean:
 	rm -rf $(BUILD) $(LIB)
 
-.PHONY: all clean asan asan-rcseg asan-rcseg-ctx
+.PHONY: all clean asan asan-rcseg asan-rcseg-ctx asan-rcseg-nbr

@@ -51,7 +51,7 @@ def my_parse_args(argv=None):
     if args.entropy == "host" and not args.raw:
         from tf_image_compression_amd.range_coder import dist_is_ctx
         if dist_is_ctx(args.dist.format(args.model_num)):
-            p.error(f"{args.dist.format(args.model_num)} holds per-context probabilities (2-D): the single-stream "
+            p.error(f"{args.dist.format(args.model_num)} holds per-context probabilities (2-D or 3-D): the single-stream "
                     "host coder has one table; use --entropy device")
     return args
 
@@ -83,14 +83,28 @@ def apply_range_decoder(seq_len, path, cum_freq):
     return out
 
 
-def check_container_version(path, stream, cum_freq, args):
+def check_container_version(path, stream, cum_freq, args, code_shape=None):
     """The coder follows the file's version byte: version 1 was coded under one table (a 1-D
-    --dist array), version 2 under per-context tables (a 2-D one)."""
+    --dist array), version 2 under per-context tables (a 2-D one), version 3 under context x
+    neighbour tables (a 3-D one) for a code geometry that must be the model's (``code_shape``)."""
     from tf_image_compression_amd import entropy
     if not entropy.is_container(stream):
         return  # entropy.parse names what it is not
     version, ctx = entropy.container_version(stream), entropy.is_ctx_table(cum_freq)
+    nbr = entropy.is_nbr_table(cum_freq)
     dist = args.dist.format(args.model_num)
+    if version == 3 and not nbr:
+        raise ValueError(f"{path} is a version-3 (neighbour) stream, but {dist} does not hold 3-D tables: pass "
+                         "the 3-D distribution it was encoded with")
+    if version != 3 and nbr:
+        raise ValueError(f"{path} is a version-{version} stream, but {dist} holds 3-D context x neighbour "
+                         "tables: pass the distribution it was encoded with")
+    if version == 3:
+        geometry = entropy.parse_nbr(stream)[4]
+        if code_shape is not None and tuple(geometry) != tuple(int(v) for v in code_shape):
+            raise ValueError(f"{path} was coded for the code geometry {geometry}, the model's at this patch size "
+                             f"is {tuple(int(v) for v in code_shape)}")
+        return
     if version == 2 and not ctx:
         raise ValueError(f"{path} is a version-2 (context) stream, but {dist} holds one 1-D table: pass the "
                          "2-D per-context distribution it was encoded with")
@@ -169,7 +183,8 @@ def uncompress(model, args):
         for group in ic.plan_batches(sizes, P, args.batch_images):
             streams = [(Path(input_dir) / filenames[i]).read_bytes() for i in group]
             for i, stream in zip(group, streams):
-                check_container_version(str(Path(input_dir) / filenames[i]), stream, cum_freq, args)
+                check_container_version(str(Path(input_dir) / filenames[i]), stream, cum_freq, args,
+                                        ic.codec.code_shape)
             images = ic.decode_streams_to_images(streams, [sizes[i] for i in group], cum_freq,
                                                  post_filter=post is not None)
             for i, recons in zip(group, images):

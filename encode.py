@@ -18,7 +18,9 @@ no checkpoint exists), ``--raw`` (store bit-packed symbols, no entropy coding),
 tf_image_compression_amd/entropy.py, which ``decode.py --entropy device`` reads).  With
 ``--entropy device`` a 2-D ``--dist`` array ([K, Q] per-context probabilities,
 get_encoded_distribution.py --context) codes symbol k of an image under table k mod K and writes
-version-2 containers.
+version-2 containers.  A 3-D array ([K0, M, Q], get_encoded_distribution.py --context --neighbours)
+also conditions every symbol on its causal neighbours' classes and writes version-3 containers; the
+geometry they carry is the model's code shape at the patch size.
 """
 import argparse
 import os
@@ -65,7 +67,7 @@ def my_parse_args(argv=None):
     if args.entropy == "host" and not args.raw:
         from tf_image_compression_amd.range_coder import dist_is_ctx
         if dist_is_ctx(args.dist.format(args.model_num)):
-            p.error(f"{args.dist.format(args.model_num)} holds per-context probabilities (2-D): the single-stream "
+            p.error(f"{args.dist.format(args.model_num)} holds per-context probabilities (2-D or 3-D): the single-stream "
                     "host coder has one table; use --entropy device")
     return args
 

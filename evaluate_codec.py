@@ -16,7 +16,9 @@ total pixels.  Without a distribution file the rate columns are omitted.  ``--en
 stream (tf_image_compression_amd/entropy.py) and prints its real size, ``coded_bytes``, and the
 bpp from it.  With ``--entropy device`` a 2-D ``--dist`` array ([K, Q] per-context probabilities,
 get_encoded_distribution.py --context) gives both under the context coder: the estimate from
-the per-context histogram, ``coded_bytes`` from version-2 containers.
+the per-context histogram, ``coded_bytes`` from version-2 containers.  A 3-D array ([K0, M, Q],
+get_encoded_distribution.py --context --neighbours) does the same under the causal-neighbour coder
+(version-3 containers; the estimate uses the rows the coder uses at ``--segment``).
 """
 import argparse
 import json
@@ -61,7 +63,7 @@ def my_parse_args(argv=None):
     if args.entropy == "host":
         from tf_image_compression_amd.range_coder import dist_is_ctx
         if dist_is_ctx(args.dist.format(args.model_num)):
-            p.error(f"{args.dist.format(args.model_num)} holds per-context probabilities (2-D): use --entropy device")
+            p.error(f"{args.dist.format(args.model_num)} holds per-context probabilities (2-D or 3-D): use --entropy device")
     return args
 
 
@@ -114,8 +116,8 @@ def run(model, args) -> dict:
     if os.path.exists(dist):
         from tf_image_compression_amd.range_coder import dist_table
         cum_freq = dist_table(np.load(dist, allow_pickle=False), resolution=config["resolution"])
-        if np.ndim(cum_freq) == 2 and getattr(args, "entropy", "host") != "device":
-            raise ValueError(f"{dist} holds per-context probabilities (2-D): use --entropy device")
+        if np.ndim(cum_freq) >= 2 and getattr(args, "entropy", "host") != "device":
+            raise ValueError(f"{dist} holds per-context probabilities (2-D or 3-D): use --entropy device")
     else:
         print(f"no symbol distribution at {dist}: the estimated rate is omitted")
     post = None

@@ -391,6 +391,45 @@ int tic_rcseg_parse_ctx(const uint8_t* buf, size_t nbytes, uint32_t* L, uint64_t
 int tic_rcseg_decode_ctx(const uint8_t* buf, size_t nbytes, const int64_t* tables, size_t K, size_t ncum,
                          uint8_t* sym_out, size_t n);
 
+/* --- segmented range-coder stream, version 3: causal-neighbour contexts (host part) ---
+ * The stream is coded under K = K0*M cumulative tables of one common ncum; nsym = ncum - 1.  The
+ * container carries the code geometry (eh, ew, C), neighbours in {1, 2} (1: W; 2: W and N) and
+ * M = 3^neighbours.  For symbol k of the stream (patch-major, then h, w, C):
+ *   p = k mod (eh*ew*C), h = p div (ew*C), w = (p div C) mod ew, seg0 = L*floor(k / L)
+ *   W neighbour jW = k - C,    valid iff w >= 1 and jW >= seg0
+ *   N neighbour jN = k - ew*C, valid iff h >= 1 and jN >= seg0
+ *   t(j) = 0 when j is invalid, else 1 + class(sym[j]); class(s) = 1 if 2*s >= nsym, else 0
+ *   nb = t(jW) (neighbours = 1), t(jW) + 3*t(jN) (neighbours = 2)
+ * and symbol k is coded under table row (k mod K0)*M + nb.  K0 = C gives channel x neighbours
+ * (the intended use); K0 = 1 and K0 = eh*ew*C are legal.  A neighbour outside the symbol's own
+ * segment never counts, so segments stay independent streams; n need not be a multiple of the
+ * patch size and L need not relate to the geometry.  The container is version 2's with a 36-byte
+ * header:
+ *   0..19  as versions 1 and 2, version byte = 3
+ *   20 4   K0                     24 4  CRC-32C (tic_crc32c) of the K*ncum table entries as int64,
+ *   28 6   u16 eh, u16 ew, u16 C        little-endian, row-major
+ *   34 1   neighbours             35 1  zero
+ *   36     the u16 length table, then the payloads
+ * A segment's payload is what tic_rc_encode writes when every symbol is passed in a call of its
+ * own under the row above.  tables: K rows, each validated as version 2 validates its rows (rows
+ * the geometry never reaches included).  1 <= eh, ew, C <= 65535, K0 >= 1, K*ncum <= 262144. */
+
+/* tic_rcseg_bound + 16. */
+int tic_rcseg_bound_nbr(size_t n, uint32_t L, size_t* bytes);
+/* As tic_rcseg_encode, under tables[K0][M][ncum]. */
+int tic_rcseg_encode_nbr(const uint8_t* sym, size_t n, uint32_t L, const int64_t* tables, size_t K0,
+                         uint32_t neighbours, size_t ncum, uint32_t eh, uint32_t ew, uint32_t C, uint8_t* out,
+                         size_t cap, size_t* written);
+/* tic_rcseg_parse's validation of a version-3 container (versions 1 and 2 are TIC_EINVAL, as
+ * version 3 is for tic_rcseg_parse and tic_rcseg_parse_ctx), the reserved byte, neighbours in
+ * {1, 2}, the geometry and K0 within their limits.  Outputs may be NULL. */
+int tic_rcseg_parse_nbr(const uint8_t* buf, size_t nbytes, uint32_t* L, uint64_t* n, uint32_t* K0, uint32_t* crc,
+                        uint32_t* eh, uint32_t* ew, uint32_t* C, uint32_t* neighbours);
+/* tic_rcseg_parse_nbr, TIC_EINVAL when n, K0, the geometry, neighbours or the CRC of `tables`
+ * differ from the header's, then the n symbols. */
+int tic_rcseg_decode_nbr(const uint8_t* buf, size_t nbytes, const int64_t* tables, size_t K0, uint32_t neighbours,
+                         size_t ncum, uint32_t eh, uint32_t ew, uint32_t C, uint8_t* sym_out, size_t n);
+
 /* --- segmented streams on the device (csrc/tic_entropy.cpp) ---
  * One range coder per lane, one segment each; a scan over the segment lengths; a gather that
  * writes the containers.  All entries are asynchronous on the handle's stream, never synchronise,
@@ -448,6 +487,34 @@ int tic_entropy_decode_ctx_device(tic_handle* h, const uint8_t* d_blob, const in
  * counts d_counts[K][Q] (8-byte aligned; accumulates, zero it first; d_sym of any alignment).
  * Integer adds only: the result does not depend on the order they happen in.  1 <= K <= 65536. */
 int tic_histogram_ctx_device(tic_handle* h, const uint8_t* d_sym, size_t n, int Q, int K, uint64_t* d_counts);
+
+/* --- version-3 (causal-neighbour) streams on the device ---
+ * The K0*M tables, the geometry and `neighbours` of the following *_nbr_device calls on this
+ * handle, validated as tic_rcseg_encode_nbr does.  They are uploaded as tic_entropy_set_tables
+ * uploads its tables, into the same per-handle buffer (so they replace version-2 tables, and
+ * tic_entropy_set_tables replaces them), ordered on the handle's stream and complete on return. */
+int tic_entropy_set_tables_nbr(tic_handle* h, const int64_t* tables, size_t K0, uint32_t neighbours, size_t ncum,
+                               uint32_t eh, uint32_t ew, uint32_t C);
+/* tic_entropy_encode_ctx_device writing version-3 containers: the same arguments and contract,
+ * out_cap at least the sum of tic_rcseg_bound_nbr.  Every stream starts at position 0 of a patch.
+ * A lane carries (c, w, h) and its K0 phase as counters and reads its neighbours from d_sym. */
+int tic_entropy_encode_nbr_device(tic_handle* h, const uint8_t* d_sym, const int64_t* sym_offsets,
+                                  const int64_t* counts, int n_streams, uint32_t L, void* d_scratch,
+                                  size_t scratch_bytes, uint8_t* d_out, size_t out_cap, uint64_t* d_sizes);
+/* tic_entropy_decode_ctx_device for version-3 containers (passed through tic_rcseg_parse_nbr by
+ * the caller).  A container whose version, K0, CRC, geometry or neighbours is not what was set
+ * decodes to zeros.  A lane keeps the classes of its own last symbols as a ring of bits in LDS
+ * (as far back as its farthest neighbour that a segment can reach); when the rings of a workgroup
+ * exceed 64 KiB it re-reads the bytes it stored itself instead.  No lane reads another's output. */
+int tic_entropy_decode_nbr_device(tic_handle* h, const uint8_t* d_blob, const int64_t* blob_offsets,
+                                  const int64_t* blob_sizes, const int64_t* counts, int n_streams, uint8_t* d_sym,
+                                  const int64_t* sym_offsets, void* d_scratch, size_t scratch_bytes);
+/* Symbol k of stream i (counts[i] symbols at d_sym + sym_offsets[i]) counts in row
+ * (k mod K0)*M + nb of the uint64 counts d_counts[K0*M][Q], nb as the coder derives it at segment
+ * length L from the geometry, K0 and neighbours last set on the handle (class(s) = 2*s >= Q;
+ * np.histogram's bins as tic_histogram_device).  Accumulates; integer adds only. */
+int tic_histogram_nbr_device(tic_handle* h, const uint8_t* d_sym, const int64_t* sym_offsets, const int64_t* counts,
+                             int n_streams, int Q, uint32_t L, uint64_t* d_counts);
 
 #ifdef __cplusplus
 }

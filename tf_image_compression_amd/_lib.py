@@ -120,6 +120,24 @@ SIGNATURES = [
                                                C.POINTER(C.c_int64), C.c_int, vp, C.POINTER(C.c_int64), vp,
                                                C.c_size_t]),
     ("tic_histogram_ctx_device", C.c_int, [vp, vp, C.c_size_t, C.c_int, C.c_int, vp]),
+    # version-3 (causal-neighbour) streams: K0 * M tables, row (k mod K0) * M + nb
+    ("tic_rcseg_bound_nbr", C.c_int, [C.c_size_t, C.c_uint32, C.POINTER(C.c_size_t)]),
+    ("tic_rcseg_encode_nbr", C.c_int, [u8p, C.c_size_t, C.c_uint32, C.POINTER(C.c_int64), C.c_size_t, C.c_uint32,
+                                      C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32, u8p, C.c_size_t,
+                                      C.POINTER(C.c_size_t)]),
+    ("tic_rcseg_parse_nbr", C.c_int, [u8p, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+                                     + [C.POINTER(C.c_uint32)] * 6),
+    ("tic_rcseg_decode_nbr", C.c_int, [u8p, C.c_size_t, C.POINTER(C.c_int64), C.c_size_t, C.c_uint32, C.c_size_t,
+                                      C.c_uint32, C.c_uint32, C.c_uint32, u8p, C.c_size_t]),
+    ("tic_entropy_set_tables_nbr", C.c_int, [vp, C.POINTER(C.c_int64), C.c_size_t, C.c_uint32, C.c_size_t, C.c_uint32,
+                                            C.c_uint32, C.c_uint32]),
+    ("tic_entropy_encode_nbr_device", C.c_int, [vp, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int,
+                                               C.c_uint32, vp, C.c_size_t, vp, C.c_size_t, vp]),
+    ("tic_entropy_decode_nbr_device", C.c_int, [vp, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                               C.POINTER(C.c_int64), C.c_int, vp, C.POINTER(C.c_int64), vp,
+                                               C.c_size_t]),
+    ("tic_histogram_nbr_device", C.c_int, [vp, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int, C.c_int,
+                                          C.c_uint32, vp]),
     ("tic_device_info", C.c_int, [vp, C.c_char_p, C.c_int]),
 ]
 

@@ -439,6 +439,56 @@ class Codec:
             raise ValueError(f"d_counts holds {d_counts.nbytes} bytes, [{K}, {Q}] counts need {8 * int(K) * int(Q)}")
         check(lib().tic_histogram_ctx_device(self._h, d_sym.ptr, n, Q, K, d_counts.ptr), "tic_histogram_ctx_device")
 
+    # version-3 (causal-neighbour) streams: K0 * M tables, symbol k under row (k mod K0) * M + nb
+    def entropy_set_tables_nbr(self, tables, geometry=None) -> None:
+        """The ``[K0, M, ncum]`` cumulative tables (``M`` = 3: W neighbour; 9: W and N) and the code
+        geometry ``(eh, ew, C)`` (default: this codec's ``code_shape``) of the following
+        ``*_nbr_device`` calls (tic_entropy_set_tables_nbr).  They share the device buffer of
+        ``entropy_set_tables`` and replace its tables."""
+        from .entropy import nbr_tables, neighbours_of
+        t = nbr_tables(tables)
+        eh, ew, c = (int(v) for v in (self.code_shape if geometry is None else geometry))
+        if not all(0 <= v < 2 ** 32 for v in (eh, ew, c)):
+            raise ValueError(f"code geometry {eh} x {ew} x {c} must be in [1, 65535] each")
+        check(lib().tic_entropy_set_tables_nbr(self._h, ptr(t, C.c_int64), t.shape[0], neighbours_of(t), t.shape[2],
+                                               eh, ew, c), "tic_entropy_set_tables_nbr")
+        self._nbr_rows = t.shape[0] * t.shape[1]
+
+    def entropy_encode_nbr_device(self, d_sym: DeviceBuffer, sym_offsets, counts, segment: int,
+                                  d_scratch: DeviceBuffer, d_out: DeviceBuffer, d_sizes: DeviceBuffer,
+                                  scratch_bytes: int | None = None, out_cap: int | None = None) -> None:
+        """``entropy_encode_device`` writing version-3 containers under the tables and geometry set
+        (tic_entropy_encode_nbr_device); every stream starts at position 0 of a patch."""
+        n, (off, cnt) = self._stream_table(sym_offsets, counts)
+        if d_sizes.nbytes < 8 * n:
+            raise ValueError(f"d_sizes holds {d_sizes.nbytes} bytes, {n} streams need {8 * n}")
+        check(lib().tic_entropy_encode_nbr_device(
+            self._h, d_sym.ptr, ptr(off, C.c_int64), ptr(cnt, C.c_int64), n, int(segment), d_scratch.ptr,
+            d_scratch.nbytes if scratch_bytes is None else int(scratch_bytes), d_out.ptr,
+            d_out.nbytes if out_cap is None else int(out_cap), d_sizes.ptr), "tic_entropy_encode_nbr_device")
+
+    def entropy_decode_nbr_device(self, d_blob: DeviceBuffer, blob_offsets, blob_sizes, counts, d_sym: DeviceBuffer,
+                                  sym_offsets, d_scratch: DeviceBuffer, scratch_bytes: int | None = None) -> None:
+        """``entropy_decode_device`` for version-3 containers (validated by ``entropy.parse_nbr``
+        before the upload) under the tables and geometry set (tic_entropy_decode_nbr_device)."""
+        n, (boff, bsz, cnt, soff) = self._stream_table(blob_offsets, blob_sizes, counts, sym_offsets)
+        check(lib().tic_entropy_decode_nbr_device(
+            self._h, d_blob.ptr, ptr(boff, C.c_int64), ptr(bsz, C.c_int64), ptr(cnt, C.c_int64), n, d_sym.ptr,
+            ptr(soff, C.c_int64), d_scratch.ptr, d_scratch.nbytes if scratch_bytes is None else int(scratch_bytes)),
+            "tic_entropy_decode_nbr_device")
+
+    def histogram_nbr_device(self, d_sym: DeviceBuffer, sym_offsets, counts, Q: int, segment: int,
+                             d_counts: DeviceBuffer):
+        """Accumulate symbol ``k`` of every stream into row ``(k mod K0) * M + nb`` of the uint64
+        counts ``d_counts[K0 * M, Q]``, ``nb`` as the coder derives it at this ``segment`` from the
+        geometry, ``K0`` and ``M`` last set by ``entropy_set_tables_nbr`` (tic_histogram_nbr_device)."""
+        n, (off, cnt) = self._stream_table(sym_offsets, counts)
+        rows = getattr(self, "_nbr_rows", 0)
+        if rows and d_counts.nbytes < 8 * rows * int(Q):
+            raise ValueError(f"d_counts holds {d_counts.nbytes} bytes, [{rows}, {Q}] counts need {8 * rows * int(Q)}")
+        check(lib().tic_histogram_nbr_device(self._h, d_sym.ptr, ptr(off, C.c_int64), ptr(cnt, C.c_int64), n, int(Q),
+                                             int(segment), d_counts.ptr), "tic_histogram_nbr_device")
+
     def round_u8_device(self, d_in: DeviceBuffer, n: int, d_out: DeviceBuffer):
         check(lib().tic_round_u8_device(self._h, d_in.ptr, n, d_out.ptr), "tic_round_u8_device")
 

@@ -251,6 +251,84 @@ int parse_framing(const uint8_t* buf, size_t nbytes, size_t header, uint32_t* L_
   if (n_out) *n_out = n;
   return TIC_OK;
 }
+
+// --- segmented stream, version 3: K0 periodic contexts x the classes of the causal neighbours ---
+constexpr size_t kNbrHeader = 36;
+
+struct NbrModel {
+  size_t K0 = 0, M = 0, ncum = 0;
+  uint32_t eh = 0, ew = 0, C = 0, neighbours = 0;
+};
+
+int check_nbr_geometry(size_t K0, uint32_t eh, uint32_t ew, uint32_t C, uint32_t neighbours, const char* what) {
+  if (neighbours != 1 && neighbours != 2)
+    return rc_fail(TIC_EINVAL, std::string(what) + ": neighbours " + std::to_string(neighbours) + " must be 1 (W) or 2 (W and N)");
+  if (eh < 1 || ew < 1 || C < 1 || eh > 65535 || ew > 65535 || C > 65535)
+    return rc_fail(TIC_EINVAL, std::string(what) + ": code geometry " + std::to_string(eh) + " x " + std::to_string(ew) + " x " +
+                                   std::to_string(C) + " must be in [1, 65535] each");
+  const size_t M = neighbours == 1 ? 3 : 9;
+  if (K0 < 1 || K0 > kCtxMaxEntries / (2 * M))
+    return rc_fail(TIC_EINVAL, std::string(what) + ": context count " + std::to_string(K0) + " must be in [1, " +
+                                   std::to_string(kCtxMaxEntries / (2 * M)) + "]");
+  return TIC_OK;
+}
+
+// K0 * M rows of one ncum, each a check_seg_table table (rows the geometry never reaches included)
+int check_nbr_tables(const int64_t* tables, const NbrModel& m, std::vector<int64_t>* totals) {
+  if (!tables) return rc_fail(TIC_EINVAL, "invalid frequency table (null)");
+  const int rc0 = check_nbr_geometry(m.K0, m.eh, m.ew, m.C, m.neighbours, "neighbour tables");
+  if (rc0) return rc0;
+  if (m.ncum < 2) return rc_fail(TIC_EINVAL, "invalid frequency table (needs >= 2 entries)");
+  if (m.ncum > 257) return rc_fail(TIC_EINVAL, "segmented streams code byte symbols: at most 257 table entries");
+  const size_t K = m.K0 * m.M;
+  if (K * m.ncum > kCtxMaxEntries)
+    return rc_fail(TIC_EINVAL, "neighbour tables of " + std::to_string(K * m.ncum) + " entries exceed the limit of 262144");
+  totals->resize(K);
+  for (size_t k = 0; k < K; ++k) {
+    const int rc = check_seg_table(tables + k * m.ncum, m.ncum, &(*totals)[k]);
+    if (rc) {
+      g_rc_err = "context " + std::to_string(k / m.M) + ", neighbours " + std::to_string(k % m.M) + ": " + g_rc_err;
+      return rc;
+    }
+  }
+  return TIC_OK;
+}
+
+// The row of every symbol of one segment, in order: (c, w, h) and the K0 phase are counters that
+// wrap, as on the device.  sym: the stream's symbols, those before the current one valid.
+struct NbrWalk {
+  const NbrModel& m;
+  const uint8_t* sym;
+  size_t b;  // the segment's first symbol
+  size_t nsym, rowC;
+  uint32_t c, w, h;
+  size_t k0;
+  NbrWalk(const NbrModel& m_, const uint8_t* sym_, size_t b_) : m(m_), sym(sym_), b(b_) {
+    nsym = m.ncum - 1;
+    rowC = (size_t)m.ew * m.C;
+    const uint64_t p = (uint64_t)b % ((uint64_t)m.eh * rowC);
+    c = (uint32_t)(p % m.C);
+    w = (uint32_t)((p / m.C) % m.ew);
+    h = (uint32_t)(p / rowC);
+    k0 = b % m.K0;
+  }
+  size_t t(size_t j) const { return 1 + (2 * (size_t)sym[j] >= nsym ? 1 : 0); }
+  size_t row(size_t i) const {  // of symbol i; then advance() before the next
+    size_t nb = (w >= 1 && i - b >= m.C) ? t(i - m.C) : 0;
+    if (m.neighbours == 2 && h >= 1 && i - b >= rowC) nb += 3 * t(i - rowC);
+    return k0 * m.M + nb;
+  }
+  void advance() {
+    if (++k0 == m.K0) k0 = 0;
+    if (++c == m.C) {
+      c = 0;
+      if (++w == m.ew) {
+        w = 0;
+        if (++h == m.eh) h = 0;
+      }
+    }
+  }
+};
 }  // namespace
 
 struct tic_rc_encoder {
@@ -531,6 +609,134 @@ int tic_rcseg_decode_ctx(const uint8_t* buf, size_t nbytes, const int64_t* table
     for (size_t i = b; i < e; ++i) {
       sym_out[i] = (uint8_t)c.symbol(tables + k * ncum, (int64_t)ncum - 1, (uint64_t)totals[k]);
       if (++k == K) k = 0;
+    }
+    p += len;
+  }
+  return TIC_OK;
+}
+
+// --- segmented stream, version 3 ---
+
+int tic_rcseg_bound_nbr(size_t n, uint32_t L, size_t* bytes) {
+  const int rc = tic_rcseg_bound(n, L, bytes);
+  if (rc) return rc;
+  *bytes += kNbrHeader - kSegHeader;
+  return TIC_OK;
+}
+
+int tic_rcseg_encode_nbr(const uint8_t* sym, size_t n, uint32_t L, const int64_t* tables, size_t K0,
+                         uint32_t neighbours, size_t ncum, uint32_t eh, uint32_t ew, uint32_t C, uint8_t* out,
+                         size_t cap, size_t* written) {
+  if (!sym || !out || !written) return rc_fail(TIC_EINVAL, "null argument");
+  *written = 0;
+  size_t bound = 0;
+  int rc = tic_rcseg_bound_nbr(n, L, &bound);
+  if (rc) return rc;
+  NbrModel m;
+  m.K0 = K0, m.M = neighbours == 1 ? 3 : 9, m.ncum = ncum, m.eh = eh, m.ew = ew, m.C = C, m.neighbours = neighbours;
+  std::vector<int64_t> totals;
+  if ((rc = check_nbr_tables(tables, m, &totals))) return rc;
+  if (cap < bound)
+    return rc_fail(TIC_EINVAL, "output of " + std::to_string(cap) + " bytes is below tic_rcseg_bound_nbr (" + std::to_string(bound) + ")");
+  const size_t S = (n + L - 1) / L, nsym = ncum - 1;
+  for (size_t i = 0; i < n; ++i)  // before any row is derived from a symbol
+    if (sym[i] >= nsym) return rc_fail(TIC_EINVAL, "symbol " + std::to_string(sym[i]) + " outside the table (cumFreq too short)");
+  memcpy(out, kSegMagic, 4);
+  wr32(out + 4, 3);  // version 3, three zero bytes
+  wr32(out + 8, L);
+  wr32(out + 12, (uint32_t)((uint64_t)n & 0xFFFFFFFFu));
+  wr32(out + 16, (uint32_t)((uint64_t)n >> 32));
+  wr32(out + 20, (uint32_t)K0);
+  wr32(out + 24, ctx_tables_crc(tables, K0 * m.M * ncum));
+  wr32(out + 28, eh | ew << 16);
+  wr32(out + 32, C | neighbours << 16);  // byte 35 stays zero
+  uint8_t* lens = out + kNbrHeader;
+  uint8_t* p = lens + 2 * S;
+  for (size_t j = 0; j < S; ++j) {
+    const size_t b = j * L, e = std::min(n, b + L);
+    EncCore<MemSink> c;
+    c.s.p = p;
+    NbrWalk walk(m, sym, b);
+    for (size_t i = b; i < e; ++i) {
+      const size_t s = sym[i], k = walk.row(i);
+      const int64_t* cum = tables + k * ncum;
+      c.symbol((uint64_t)cum[s], (uint64_t)(cum[s + 1] - cum[s]), (uint64_t)totals[k], cum[s + 1] == totals[k]);
+      walk.advance();
+    }
+    c.finish();
+    const size_t len = (size_t)(c.s.p - p);
+    lens[2 * j] = (uint8_t)(len & 0xFF);
+    lens[2 * j + 1] = (uint8_t)(len >> 8);
+    p = c.s.p;
+  }
+  *written = (size_t)(p - out);
+  return TIC_OK;
+}
+
+int tic_rcseg_parse_nbr(const uint8_t* buf, size_t nbytes, uint32_t* L_out, uint64_t* n_out, uint32_t* K0_out,
+                        uint32_t* crc_out, uint32_t* eh_out, uint32_t* ew_out, uint32_t* C_out,
+                        uint32_t* neighbours_out) {
+  if (!buf) return rc_fail(TIC_EINVAL, "null argument");
+  if (nbytes < kSegHeader) return rc_fail(TIC_EINVAL, "not a segmented stream: shorter than its 20-byte header");
+  if (memcmp(buf, kSegMagic, 4) != 0) return rc_fail(TIC_EINVAL, "not a segmented stream: magic is not \"TICS\"");
+  if (buf[4] != 3)
+    return rc_fail(TIC_EINVAL, "segmented stream version " + std::to_string(buf[4]) + " is not a neighbour stream (version 3)");
+  if (buf[5] || buf[6] || buf[7]) return rc_fail(TIC_EINVAL, "segmented stream: reserved bytes are not zero");
+  if (nbytes < kNbrHeader) return rc_fail(TIC_EINVAL, "neighbour stream: shorter than its 36-byte header");
+  if (buf[35]) return rc_fail(TIC_EINVAL, "neighbour stream: reserved byte is not zero");
+  const uint32_t K0 = rd32(buf + 20);
+  const uint32_t eh = buf[28] | (uint32_t)buf[29] << 8, ew = buf[30] | (uint32_t)buf[31] << 8,
+                 C = buf[32] | (uint32_t)buf[33] << 8, nb = buf[34];
+  int rc = check_nbr_geometry(K0, eh, ew, C, nb, "neighbour stream");
+  if (rc) return rc;
+  if ((rc = parse_framing(buf, nbytes, kNbrHeader, L_out, n_out))) return rc;
+  if (K0_out) *K0_out = K0;
+  if (crc_out) *crc_out = rd32(buf + 24);
+  if (eh_out) *eh_out = eh;
+  if (ew_out) *ew_out = ew;
+  if (C_out) *C_out = C;
+  if (neighbours_out) *neighbours_out = nb;
+  return TIC_OK;
+}
+
+int tic_rcseg_decode_nbr(const uint8_t* buf, size_t nbytes, const int64_t* tables, size_t K0, uint32_t neighbours,
+                         size_t ncum, uint32_t eh, uint32_t ew, uint32_t C, uint8_t* sym_out, size_t n) {
+  if (!sym_out) return rc_fail(TIC_EINVAL, "null argument");
+  uint32_t L = 0, hK0 = 0, hcrc = 0, heh = 0, hew = 0, hC = 0, hnb = 0;
+  uint64_t hn = 0;
+  int rc = tic_rcseg_parse_nbr(buf, nbytes, &L, &hn, &hK0, &hcrc, &heh, &hew, &hC, &hnb);
+  if (rc) return rc;
+  if (hn != (uint64_t)n)
+    return rc_fail(TIC_EINVAL, "segmented stream holds " + std::to_string(hn) + " symbols, " + std::to_string(n) + " expected");
+  NbrModel m;
+  m.K0 = K0, m.M = neighbours == 1 ? 3 : 9, m.ncum = ncum, m.eh = eh, m.ew = ew, m.C = C, m.neighbours = neighbours;
+  std::vector<int64_t> totals;
+  if ((rc = check_nbr_tables(tables, m, &totals))) return rc;
+  if ((size_t)hK0 != K0)
+    return rc_fail(TIC_EINVAL, "neighbour stream was coded under " + std::to_string(hK0) + " contexts, " + std::to_string(K0) + " given");
+  if (heh != eh || hew != ew || hC != C)
+    return rc_fail(TIC_EINVAL, "neighbour stream was coded for the geometry " + std::to_string(heh) + " x " + std::to_string(hew) +
+                                   " x " + std::to_string(hC) + ", " + std::to_string(eh) + " x " + std::to_string(ew) + " x " +
+                                   std::to_string(C) + " given");
+  if (hnb != neighbours)
+    return rc_fail(TIC_EINVAL, "neighbour stream was coded with neighbours " + std::to_string(hnb) + ", " + std::to_string(neighbours) + " given");
+  if (hcrc != ctx_tables_crc(tables, K0 * m.M * ncum))
+    return rc_fail(TIC_EINVAL, "neighbour stream: the tables' CRC-32C differs from the header's (coded under other tables)");
+  const size_t S = (n + L - 1) / L;
+  const uint8_t* lens = buf + kNbrHeader;
+  const uint8_t* p = lens + 2 * S;
+  for (size_t j = 0; j < S; ++j) {
+    const size_t len = (size_t)lens[2 * j] | (size_t)lens[2 * j + 1] << 8;
+    const size_t b = j * L, e = std::min(n, b + L);
+    DecCore<MemSource> c;
+    c.s.p = p;
+    c.s.end = p + len;
+    c.start();
+    NbrWalk walk(m, sym_out, b);
+    for (size_t i = b; i < e; ++i) {
+      const size_t k = walk.row(i);
+      sym_out[i] = (uint8_t)c.symbol(tables + k * ncum, (int64_t)ncum - 1, (uint64_t)totals[k]);
+      walk.advance();
     }
     p += len;
   }

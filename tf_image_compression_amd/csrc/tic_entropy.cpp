@@ -1,4 +1,4 @@
-// tic_entropy.cpp — the segmented range-coder stream (include/tic.h, "TICS" versions 1 and 2) coded on
+// tic_entropy.cpp — the segmented range-coder stream (include/tic.h, "TICS" versions 1 to 3) coded on
 // the device, and its C-ABI entries.
 //
 // The single-stream coder of range_coder.cpp is one latency chain per image.  A segmented stream
@@ -46,6 +46,11 @@
 // stay as they were.  K tables do not fit kernel arguments: tic_entropy_set_tables uploads them to
 // a device buffer kept in the same per-handle entry, which the tic_destroy wrapper frees.
 // ent_histogram_ctx_kernel counts symbols per context for estimating such tables.
+//
+// Version 3 (K0 periodic contexts x the classes of a symbol's causal neighbours; 36-byte header
+// with K0, the CRC, the code geometry and `neighbours`) is a third instance of the templates and
+// a third pair of coder kernels, ent_encode_nbr_kernel / ent_decode_nbr_kernel, with
+// ent_histogram_nbr_kernel for its tables; they follow the version-2 kernels below.
 //
 // This file closes the one translation unit of the host runtime (it includes tic_msssim.cpp).
 #define tic_destroy tic_destroy_runtime_
@@ -234,7 +239,7 @@ __global__ void __launch_bounds__(64) ent_encode_kernel(const EntModel m, const 
 }
 
 // Workgroup i: exclusive scan of stream i's segment lengths; its container size.  HDR: the
-// header's bytes, 20 (version 1) or 28 (version 2), here and in the kernels below.
+// header's bytes, 20 (version 1), 28 (version 2) or 36 (version 3), here and in the kernels below.
 template <int HDR>
 __global__ void __launch_bounds__(256) ent_seg_scan_kernel(const EntRec* __restrict__ rec,
                                                            const unsigned long long* __restrict__ seg_base,
@@ -285,7 +290,8 @@ __global__ void __launch_bounds__(256) ent_stream_scan_kernel(const unsigned lon
 }
 
 // Workgroup g: segment g's payload, its length and (first segment) the header to their places.
-// K, crc: the version-2 header's two words (unused by version 1).
+// K, crc: the version-2 header's two words (unused by version 1); g0, g1: version 3's two more
+// (eh | ew << 16, C | neighbours << 16), K then being K0.
 template <int HDR>
 __global__ void __launch_bounds__(256) ent_gather_kernel(const EntRec* __restrict__ rec,
                                                          const unsigned long long* __restrict__ seg_base,
@@ -294,7 +300,8 @@ __global__ void __launch_bounds__(256) ent_gather_kernel(const EntRec* __restric
                                                          const unsigned long long* __restrict__ seg_off,
                                                          const unsigned long long* __restrict__ sizes,
                                                          const unsigned long long* __restrict__ out_off,
-                                                         uint32_t K, uint32_t crc, uint8_t* __restrict__ out) {
+                                                         uint32_t K, uint32_t crc, uint32_t g0, uint32_t g1,
+                                                         uint8_t* __restrict__ out) {
   const unsigned long long g = blockIdx.x;
   const int i = ent_find(seg_base, n_streams, g);
   if (sizes[i] == ~0ull) return;
@@ -306,11 +313,13 @@ __global__ void __launch_bounds__(256) ent_gather_kernel(const EntRec* __restric
     const unsigned long long n = (unsigned long long)rec[i].count;
     uint32_t b;
     if (t < 4) b = (0x53434954u >> (8 * t)) & 0xFFu;  // "TICS"
-    else if (t < 8) b = t == 4 ? (HDR == 28 ? 2u : 1u) : 0u;
+    else if (t < 8) b = t == 4 ? (HDR == 36 ? 3u : HDR == 28 ? 2u : 1u) : 0u;
     else if (t < 12) b = (L >> (8 * (t - 8))) & 0xFFu;
     else if (t < 20) b = (uint32_t)(n >> (8 * (t - 12))) & 0xFFu;
     else if (t < 24) b = (K >> (8 * (t - 20))) & 0xFFu;
-    else b = (crc >> (8 * (t - 24))) & 0xFFu;
+    else if (t < 28) b = (crc >> (8 * (t - 24))) & 0xFFu;
+    else if (t < 32) b = (g0 >> (8 * (t - 28))) & 0xFFu;
+    else b = (g1 >> (8 * (t - 32))) & 0xFFu;
     base[t] = (uint8_t)b;
   }
   if (t < 2) base[HDR + 2 * j + t] = (uint8_t)(len >> (8 * t));
@@ -320,10 +329,11 @@ __global__ void __launch_bounds__(256) ent_gather_kernel(const EntRec* __restric
 }
 
 // Lane k: the header of container first + k against the caller's count and size and, version 2,
-// against the K and the CRC of the tables set.
+// against the K and the CRC of the tables set and, version 3, the geometry words g0, g1 as well.
 template <int HDR>
 __global__ void __launch_bounds__(64) ent_dec_header_kernel(const EntChunk t, const uint8_t* __restrict__ blob,
-                                                            uint32_t K, uint32_t crc, EntRec* __restrict__ rec,
+                                                            uint32_t K, uint32_t crc, uint32_t g0, uint32_t g1,
+                                                            EntRec* __restrict__ rec,
                                                             unsigned long long* __restrict__ seg_cnt) {
   const int k = threadIdx.x;
   if (k >= t.n) return;
@@ -341,15 +351,23 @@ __global__ void __launch_bounds__(64) ent_dec_header_kernel(const EntChunk t, co
     unsigned long long n = 0;
     for (int b = 0; b < 4; ++b) L |= (uint32_t)p[8 + b] << (8 * b);
     for (int b = 0; b < 8; ++b) n |= (unsigned long long)p[12 + b] << (8 * b);
-    bool ok = p[0] == 'T' && p[1] == 'I' && p[2] == 'C' && p[3] == 'S' && p[4] == (HDR == 28 ? 2 : 1) && !p[5] &&
+    bool ok = p[0] == 'T' && p[1] == 'I' && p[2] == 'C' && p[3] == 'S' && p[4] == (HDR == 36 ? 3 : HDR == 28 ? 2 : 1) && !p[5] &&
               !p[6] && !p[7];
-    if (HDR == 28) {
+    if (HDR >= 28) {
       uint32_t hk = 0, hc = 0;
       for (int b = 0; b < 4; ++b) {
         hk |= (uint32_t)p[20 + b] << (8 * b);
         hc |= (uint32_t)p[24 + b] << (8 * b);
       }
       ok = ok && hk == K && hc == crc;
+    }
+    if (HDR == 36) {
+      uint32_t h0 = 0, h1 = 0;
+      for (int b = 0; b < 4; ++b) {
+        h0 |= (uint32_t)p[28 + b] << (8 * b);
+        h1 |= (uint32_t)p[32 + b] << (8 * b);
+      }
+      ok = ok && h0 == g0 && h1 == g1;
     }
     ok = ok && L >= 4 && L <= kEntMaxL && (L & 3) == 0 && n == (unsigned long long)r.count;
     if (ok) {
@@ -730,6 +748,360 @@ __global__ void __launch_bounds__(256) ent_histogram_ctx_kernel(const uint8_t* _
   if (run) atomicAdd(&mine[cur], (unsigned long long)run);
 }
 
+// --- version 3: K0 periodic contexts x the classes of the causal neighbours (include/tic.h) ---
+//
+// The tables lie in the handle's buffer in version 2's layout, K0 * M rows; symbol k's row is
+// (k mod K0) * M + nb.  A lane carries its place in the code as counters that wrap: (c, w, h) and
+// the word offset of its K0 phase, advanced by M * ncum per symbol; the one division is at the
+// start of a segment.  A neighbour counts only inside the lane's own segment (k - C >= 0 or
+// k - ew*C >= 0 in segment-local k), so no lane needs another lane's symbols.
+//   encoder  reads the neighbours' symbols from its input, off the low / range chain
+//   decoder  RING: the classes of the lane's last `ring` symbols are a ring of bits in LDS (word i
+//            of lane l at [i * 64 + l]: lanes never share a bank).  ring is the distance of the
+//            farthest neighbour a segment can reach (ew*C, or C when neighbours = 1 or ew*C is
+//            not below the longest segment), so the bit about to be overwritten is that
+//            neighbour's and the W bit lies C behind it.  The word under the write position is
+//            held in a register and goes back to LDS when the position leaves it.  Bits of an
+//            earlier segment are never used: the validity tests come first.
+//            !RING (the rings of a workgroup over 64 KiB): every symbol is stored as a byte at
+//            once and the lane re-reads the bytes it stored itself.
+// The coder arithmetic is a third copy of ent_encode_kernel's / ent_decode_kernel's (the measured
+// kernels stay as they are): a fix to the carry, flush or renormalisation goes into all three.
+struct EntNbr {
+  uint32_t K0, M, ncum, two;   // two: the N neighbour counts (neighbours = 2)
+  uint32_t eh, ew, C, rowC;    // rowC = ew * C (below 2^32: each at most 65535)
+  uint32_t ring;               // decoder: bits of a lane's ring (0: no neighbour lies inside any segment)
+};
+
+struct EntNbrPos {
+  uint32_t c, w, h, row;  // row: word offset of table row (k mod K0) * M
+  __device__ __forceinline__ void start(const EntNbr& q, unsigned long long o) {
+    const unsigned long long p = o % ((unsigned long long)q.eh * q.rowC);
+    h = (uint32_t)(p / q.rowC);
+    const uint32_t r = (uint32_t)(p - (unsigned long long)h * q.rowC);
+    w = r / q.C;
+    c = r - w * q.C;
+    row = (uint32_t)(o % q.K0) * q.M * q.ncum;
+  }
+  __device__ __forceinline__ void advance(const EntNbr& q, uint32_t words) {
+    row += q.M * q.ncum;
+    if (row == words) row = 0;
+    if (++c == q.C) {
+      c = 0;
+      if (++w == q.ew) {
+        w = 0;
+        if (++h == q.eh) h = 0;
+      }
+    }
+  }
+};
+
+template <int LDS>
+__global__ void __launch_bounds__(64) ent_encode_nbr_kernel(const uint32_t* __restrict__ g_tab, const EntNbr q,
+                                                            const uint8_t* __restrict__ sym,
+                                                            const EntRec* __restrict__ rec,
+                                                            const unsigned long long* __restrict__ seg_base,
+                                                            int n_streams, uint32_t L, uint8_t* __restrict__ slots,
+                                                            uint32_t* __restrict__ seg_len) {
+  extern __shared__ uint32_t s_dyn[];
+  const uint32_t ncum = q.ncum, words = q.K0 * q.M * ncum;
+  if (LDS) {
+    for (uint32_t k = threadIdx.x; k < words; k += 64) s_dyn[k] = g_tab[k];
+    __syncthreads();
+  }
+  auto tab = [&](uint32_t k) -> uint32_t { return LDS ? s_dyn[k] : g_tab[k]; };
+  const unsigned long long T = seg_base[n_streams];
+  const unsigned long long g = (unsigned long long)blockIdx.x * 64 + threadIdx.x;
+  if (g >= T) return;
+  const int i = ent_find(seg_base, n_streams, g);
+  const unsigned long long j = g - seg_base[i];
+  const long long left = rec[i].count - (long long)(j * L);
+  const uint32_t cnt = left < (long long)L ? (uint32_t)left : L;
+  const uint8_t* src = sym + rec[i].in_off + (long long)(j * L);
+  uint32_t* out = reinterpret_cast<uint32_t*>(slots + (size_t)g * ent_stride(L));
+
+  const uint32_t nsym = ncum - 1;
+  EntNbrPos at;
+  at.start(q, j * L);  // every stream starts at position 0 of a patch
+  unsigned long long low = 0, range = 1ull << 32;
+  int cache = -1;
+  uint32_t pending = 0, nout = 0, acc = 0;
+  bool bad = false;
+
+  auto put = [&](uint32_t b) {
+    acc |= (b & 0xFFu) << (8 * (nout & 3));
+    ++nout;
+    if ((nout & 3) == 0) {
+      out[(nout >> 2) - 1] = acc;
+      acc = 0;
+    }
+  };
+  auto emit_top = [&]() {
+    if (low < 0xFF000000ull || low >= (1ull << 32)) {
+      const uint32_t carry = low >= (1ull << 32) ? 1u : 0u;
+      if (cache >= 0) put((uint32_t)cache + carry);
+      for (; pending; --pending) put(0xFFu + carry);
+      cache = (int)((low >> 24) & 0xFF);
+    } else {
+      ++pending;
+    }
+    low = (low << 8) & 0xFFFFFFFFull;
+  };
+  // symbol s at segment-local index k; clsW, clsN: the classes of the symbols at k - C and k - ew*C
+  // (read only where that index lies inside the segment)
+  auto step = [&](uint32_t k, uint32_t s, uint32_t clsW, uint32_t clsN) {
+    uint32_t nb = 0;
+    if (at.w && k >= q.C) nb = 1u + clsW;
+    if (q.two && at.h && k >= q.rowC) nb += 3u * (1u + clsN);
+    const uint32_t r0 = at.row + nb * ncum;
+    at.advance(q, words);
+    if (s >= nsym) {
+      bad = true;
+      return;
+    }
+    const uint32_t start = s ? tab(r0 + s - 1) : 0u, next = tab(r0 + s), total = tab(r0 + nsym - 1);
+    const int shift = (int)tab(r0 + nsym);
+    unsigned long long r;
+    if (shift >= 0) r = range >> shift;
+    else if (range >> 32) r = range / total;
+    else r = (uint32_t)range / total;
+    const unsigned long long sr = (unsigned long long)start * r;
+    low += sr;
+    range = next == total ? range - sr : (unsigned long long)(next - start) * r;
+    while (range < (1ull << 24)) {
+      range <<= 8;
+      emit_top();
+    }
+  };
+
+  auto cls = [&](uint32_t j) -> uint32_t { return 2u * src[j] >= nsym ? 1u : 0u; };
+  auto one = [&](uint32_t k) {
+    step(k, src[k], k >= q.C ? cls(k - q.C) : 0u, q.two && k >= q.rowC ? cls(k - q.rowC) : 0u);
+  };
+  uint32_t k = 0;
+  for (; k < cnt && ((uintptr_t)(src + k) & 15) != 0; ++k) one(k);
+  for (; k + 16 <= cnt; k += 16) {
+    const uint4 v = *reinterpret_cast<const uint4*>(src + k);
+    // the block's 16 + 16 neighbour classes as bit masks: independent loads, all in flight before
+    // the chain of 16 symbols starts, instead of two loads inside every step
+    uint32_t mW = 0, mN = 0;
+    if (k + 15 >= q.C) {
+#pragma unroll
+      for (int b = 0; b < 16; ++b)
+        if (k + b >= q.C) mW |= cls(k + b - q.C) << b;
+    }
+    if (q.two && k + 15 >= q.rowC) {
+#pragma unroll
+      for (int b = 0; b < 16; ++b)
+        if (k + b >= q.rowC) mN |= cls(k + b - q.rowC) << b;
+    }
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int qq = 0; qq < 4; ++qq) {
+      uint32_t x = w[qq];
+#pragma unroll 1
+      for (int b = 0; b < 4; ++b) {
+        step(k + 4 * qq + b, x & 0xFFu, mW & 1u, mN & 1u);
+        x >>= 8;
+        mW >>= 1;
+        mN >>= 1;
+      }
+    }
+  }
+  for (; k < cnt; ++k) one(k);
+
+  // the minimal flush (range_coder.cpp EncCore::finish)
+  int nb = 0;
+  unsigned long long v = low;
+  for (; nb <= 4; ++nb) {
+    if (nb == 4) {
+      v = low;
+    } else {
+      const unsigned long long unit = 1ull << (32 - 8 * nb);
+      v = (low + unit - 1) & ~(unit - 1);
+    }
+    if (v < low + range) break;
+  }
+  low = v;
+  for (int qq = 0; qq < nb; ++qq) emit_top();
+  if (nb > 0) {
+    if (cache >= 0) put((uint32_t)cache);
+    for (; pending; --pending) put(0xFFu);
+  } else if (cache >= 0) {
+    const uint32_t carry = v >= (1ull << 32) ? 1u : 0u;
+    put((uint32_t)cache + carry);
+    for (; pending; --pending) put(0xFFu + carry);
+  }
+  if (nout & 3) out[nout >> 2] = acc;  // the slot is a multiple of 4 bytes
+  seg_len[g] = bad ? kEntBad : nout;
+}
+
+// One segment per lane, grid-stride.  Dynamic LDS: the tables (LDS), then the rings (RING).
+// d_sym is not __restrict__: with !RING a lane loads bytes it stored.
+template <int LDS, int RING>
+__global__ void __launch_bounds__(64) ent_decode_nbr_kernel(const uint32_t* __restrict__ g_tab, const EntNbr q,
+                                                            const uint8_t* __restrict__ blob,
+                                                            const EntRec* __restrict__ rec,
+                                                            const unsigned long long* __restrict__ seg_base,
+                                                            int n_streams,
+                                                            const unsigned long long* __restrict__ seg_off,
+                                                            uint8_t* d_sym) {
+  extern __shared__ uint32_t s_dyn[];
+  const unsigned long long T = seg_base[n_streams];
+  if ((unsigned long long)blockIdx.x * 64 >= T) return;
+  const uint32_t ncum = q.ncum, words = q.K0 * q.M * ncum;
+  if (LDS) {
+    for (uint32_t k = threadIdx.x; k < words; k += 64) s_dyn[k] = g_tab[k];
+    __syncthreads();
+  }
+  auto tab = [&](uint32_t k) -> uint32_t { return LDS ? s_dyn[k] : g_tab[k]; };
+  uint32_t* ring = s_dyn + (LDS ? words : 0) + threadIdx.x;  // this lane's words, 64 apart
+  const uint32_t R = q.ring;
+  const bool useN = q.two && q.rowC == R;  // else no segment reaches its N neighbour
+  const uint32_t nsym = ncum - 1;
+  const bool two = ncum == 3;
+
+  for (unsigned long long g = (unsigned long long)blockIdx.x * 64 + threadIdx.x; g < T;
+       g += (unsigned long long)gridDim.x * 64) {
+    const int i = ent_find(seg_base, n_streams, g);
+    const EntRec r = rec[i];
+    if (!r.valid) continue;
+    const unsigned long long j = g - seg_base[i];
+    const long long left = r.count - (long long)(j * r.L);
+    const uint32_t cnt = left < (long long)r.L ? (uint32_t)left : r.L;
+    const uint8_t* cont = blob + r.in_off;
+    const uint32_t len = (uint32_t)cont[36 + 2 * j] | (uint32_t)cont[36 + 2 * j + 1] << 8;
+    // the segment's extent, clamped to the container
+    const unsigned long long size = (unsigned long long)r.in_size;
+    unsigned long long pos = seg_off[g];
+    if (pos > size) pos = size;
+    unsigned long long end = pos + len;
+    if (end > size) end = size;
+    uint8_t* dst = d_sym + r.out_off + (long long)(j * r.L);
+    EntNbrPos at;
+    at.start(q, j * r.L);
+    uint32_t rp = 0, rw = R ? (R - q.C % R) % R : 0;  // ring places of symbol k - R and of symbol k - C
+    // the ring word that holds place rp, kept in a register and written back when rp leaves it
+    uint32_t far = RING && R ? ring[0] : 0u;
+
+    auto get = [&]() -> uint32_t { return pos < end ? (uint32_t)cont[pos++] : 0u; };
+    uint32_t code = 0;
+    for (int b = 0; b < 4; ++b) code = (code << 8) | get();
+    unsigned long long range = 1ull << 32;
+    // symbol at segment-local index k
+    auto dec = [&](uint32_t k) -> uint32_t {
+      uint32_t nb = 0;
+      if (RING) {
+        if (R) {
+          // a place in the word under rp is read from the register: the word in LDS is older
+          const uint32_t near = (rw >> 5) == (rp >> 5) ? far : ring[(rw >> 5) * 64];
+          if (at.w && k >= q.C) nb = 1u + ((near >> (rw & 31)) & 1u);
+          if (useN && at.h && k >= R) nb += 3u * (1u + ((far >> (rp & 31)) & 1u));
+        }
+      } else {
+        if (at.w && k >= q.C) nb = 1u + (2u * dst[k - q.C] >= nsym ? 1u : 0u);
+        if (q.two && at.h && k >= q.rowC) nb += 3u * (1u + (2u * dst[k - q.rowC] >= nsym ? 1u : 0u));
+      }
+      const uint32_t r0 = at.row + nb * ncum;
+      at.advance(q, words);
+      const uint32_t total = tab(r0 + nsym - 1);
+      const int shift = (int)tab(r0 + nsym);
+      unsigned long long rr;
+      if (shift >= 0) rr = range >> shift;
+      else if (range >> 32) rr = range / total;
+      else rr = (uint32_t)range / total;
+      uint32_t val = (rr >> 32) ? 0u : code / (uint32_t)rr;
+      if (val >= total) val = total - 1;
+      uint32_t s, start, next;
+      if (two) {
+        const uint32_t c1 = tab(r0);
+        s = val >= c1 ? 1u : 0u;
+        start = s ? c1 : 0u;
+        next = s ? total : c1;
+      } else {
+        uint32_t lo = 0, hi = nsym - 1;  // last s with cum[s] <= val; cum[mid] is word mid - 1, mid >= 1
+        while (lo < hi) {
+          const uint32_t mid = (lo + hi + 1) >> 1;
+          if (tab(r0 + mid - 1) <= val) lo = mid;
+          else hi = mid - 1;
+        }
+        s = lo;
+        start = s ? tab(r0 + s - 1) : 0u;
+        next = tab(r0 + s);
+      }
+      const unsigned long long sr = (unsigned long long)start * rr;
+      code -= (uint32_t)sr;
+      range = next == total ? range - sr : (unsigned long long)(next - start) * rr;
+      while (range < (1ull << 24)) {
+        range <<= 8;
+        code = (code << 8) | get();
+      }
+      if (RING && R) {  // this symbol's class replaces that of symbol k - R
+        const uint32_t bit = 1u << (rp & 31), word = rp >> 5;
+        far = 2u * s >= nsym ? far | bit : far & ~bit;
+        if (++rp == R) rp = 0;
+        if (++rw == R) rw = 0;
+        if ((rp >> 5) != word) {
+          ring[word * 64] = far;
+          far = ring[(rp >> 5) * 64];
+        }
+      }
+      return s;
+    };
+
+    if (RING) {
+      uint32_t k = 0;
+      for (; k < cnt && ((uintptr_t)(dst + k) & 3) != 0; ++k) dst[k] = (uint8_t)dec(k);
+      for (; k + 4 <= cnt; k += 4) {
+        uint32_t w = 0;
+#pragma unroll 1
+        for (int b = 0; b < 4; ++b) w |= dec(k + b) << (8 * b);
+        *reinterpret_cast<uint32_t*>(dst + k) = w;
+      }
+      for (; k < cnt; ++k) dst[k] = (uint8_t)dec(k);
+    } else {
+      for (uint32_t k = 0; k < cnt; ++k) dst[k] = (uint8_t)dec(k);
+    }
+  }
+}
+
+// blockIdx.y: stream t.first + y of the chunk.  A thread takes pieces of 64 symbols, none across a
+// segment, finds its place once per piece and then walks the counters as the coders do.
+// np.histogram semantics as histogram_kernel (v == Q counts in the last bin, larger values in
+// none; a neighbour's class is that of its bin).  Integer adds: the sums do not depend on their order.
+__global__ void __launch_bounds__(256) ent_histogram_nbr_kernel(const EntChunk t, const EntNbr q,
+                                                                const uint8_t* __restrict__ sym, int Q, uint32_t L,
+                                                                unsigned long long* __restrict__ counts) {
+  const int i = blockIdx.y;
+  if (i >= t.n) return;
+  const unsigned long long n = (unsigned long long)t.count[i];
+  const uint8_t* src = sym + t.in_off[i];
+  const unsigned long long per = (L + 63) / 64, pieces = ((n + L - 1) / L) * per;
+  const uint32_t uq = (uint32_t)Q, rows = q.K0 * q.M;
+  auto bin = [&](uint32_t v) { return v >= uq ? uq - 1 : v; };
+  for (unsigned long long pc = (unsigned long long)blockIdx.x * 256 + threadIdx.x; pc < pieces;
+       pc += (unsigned long long)gridDim.x * 256) {
+    const unsigned long long seg0 = (pc / per) * L, a = seg0 + (pc % per) * 64;
+    unsigned long long e = a + 64;
+    if (e > seg0 + L) e = seg0 + L;
+    if (e > n) e = n;
+    if (a >= e) continue;
+    EntNbr rowsOnly = q;
+    rowsOnly.ncum = 1;  // `row` then counts table rows, not words
+    EntNbrPos at;
+    at.start(rowsOnly, a);
+    for (unsigned long long k = a; k < e; ++k) {
+      uint32_t nb = 0;
+      if (at.w && k - seg0 >= q.C) nb = 1u + (2u * bin(src[k - q.C]) >= uq ? 1u : 0u);
+      if (q.two && at.h && k - seg0 >= q.rowC) nb += 3u * (1u + (2u * bin(src[k - q.rowC]) >= uq ? 1u : 0u));
+      const uint32_t row = at.row + nb;
+      at.advance(rowsOnly, rows);
+      const uint32_t v = src[k];
+      if (v <= uq) atomicAdd(&counts[(size_t)row * Q + bin(v)], 1ull);
+    }
+  }
+}
+
 }  // namespace tic
 
 namespace {
@@ -740,6 +1112,8 @@ struct EntTables {
   uint32_t* d_tab = nullptr;
   size_t cap_words = 0;
   uint32_t K = 0, ncum = 0, crc = 0;
+  // version 3 (tic_entropy_set_tables_nbr; neighbours == 0: the tables are version 2's): K = K0 * M
+  uint32_t K0 = 0, neighbours = 0, eh = 0, ew = 0, C = 0;
 };
 struct EntState {
   tic::EntModel m;
@@ -810,25 +1184,43 @@ int ent_model(tic_handle* h, tic::EntModel* m) {
   return TIC_OK;
 }
 
-int ent_tables(tic_handle* h, EntTables* t) {
+int ent_tables(tic_handle* h, EntTables* t, bool nbr = false) {
   std::lock_guard<std::mutex> lk(g_ent_mu);
   auto it = g_ent.find(h);
-  if (it == g_ent.end() || !it->second.t.d_tab || !it->second.t.K)
+  const bool have = it != g_ent.end() && it->second.t.d_tab && it->second.t.K;
+  if (nbr && (!have || !it->second.t.neighbours))
+    return fail(TIC_EINVAL, "no neighbour tables set on this handle (tic_entropy_set_tables_nbr)");
+  if (!nbr && (!have || it->second.t.neighbours))
     return fail(TIC_EINVAL, "no context tables set on this handle (tic_entropy_set_tables)");
   *t = it->second.t;
   return TIC_OK;
 }
 
+// The kernels' view of version-3 tables; ring: the farthest neighbour a segment can reach.
+tic::EntNbr ent_nbr(const EntTables& t) {
+  tic::EntNbr q;
+  q.K0 = t.K0;
+  q.M = t.neighbours == 2 ? 9 : 3;
+  q.ncum = t.ncum;
+  q.two = t.neighbours == 2;
+  q.eh = t.eh, q.ew = t.ew, q.C = t.C;
+  q.rowC = t.ew * t.C;
+  q.ring = q.two && q.rowC < tic::kEntMaxL ? q.rowC : (q.C < tic::kEntMaxL ? q.C : 0);
+  return q;
+}
+
 constexpr size_t kEntLdsTables = 64 * 1024;  // tables up to this many bytes are staged in LDS
+constexpr size_t kEntLdsRings = 64 * 1024;   // a workgroup's class rings up to this many bytes live in LDS
 
 // Both coders' launches differ between the versions only in the header size, the table's source
-// and the coder kernel: ctx runs version 2.
+// and the coder kernel: ver is the container version.
 int ent_encode(tic_handle* h, const uint8_t* d_sym, const int64_t* sym_offsets, const int64_t* counts, int n_streams,
                uint32_t L, void* d_scratch, size_t scratch_bytes, uint8_t* d_out, size_t out_cap, uint64_t* d_sizes,
-               bool ctx);
+               int ver);
 int ent_decode(tic_handle* h, const uint8_t* d_blob, const int64_t* blob_offsets, const int64_t* blob_sizes,
                const int64_t* counts, int n_streams, uint8_t* d_sym, const int64_t* sym_offsets, void* d_scratch,
-               size_t scratch_bytes, bool ctx);
+               size_t scratch_bytes, int ver);
+int ent_upload_tables(tic_handle* h, const int64_t* tables, size_t K, size_t ncum, EntTables meta);
 
 }  // namespace
 
@@ -880,8 +1272,35 @@ int tic_entropy_set_tables(tic_handle* h, const int64_t* tables, size_t K, size_
   size_t w = 0;
   const int rc = tic_rcseg_encode_ctx(&zero, 1, 4, tables, K, ncum, out, sizeof(out), &w);
   if (rc) return fail(rc, "%s", tic_rc_last_error());
-  uint32_t crc = 0;
-  for (int b = 0; b < 4; ++b) crc |= (uint32_t)out[24 + b] << (8 * b);
+  EntTables meta;
+  for (int b = 0; b < 4; ++b) meta.crc |= (uint32_t)out[24 + b] << (8 * b);
+  return ent_upload_tables(h, tables, K, ncum, meta);
+}
+
+int tic_entropy_set_tables_nbr(tic_handle* h, const int64_t* tables, size_t K0, uint32_t neighbours, size_t ncum,
+                               uint32_t eh, uint32_t ew, uint32_t C) {
+  if (!h) return fail(TIC_EINVAL, "null handle");
+  // the host coder's own check of the tables and the geometry, and the CRC: one symbol through
+  // tic_rcseg_encode_nbr
+  const uint8_t zero = 0;
+  uint8_t out[64];
+  size_t w = 0;
+  const int rc = tic_rcseg_encode_nbr(&zero, 1, 4, tables, K0, neighbours, ncum, eh, ew, C, out, sizeof(out), &w);
+  if (rc) return fail(rc, "%s", tic_rc_last_error());
+  EntTables meta;
+  for (int b = 0; b < 4; ++b) meta.crc |= (uint32_t)out[24 + b] << (8 * b);
+  meta.K0 = (uint32_t)K0;
+  meta.neighbours = neighbours;
+  meta.eh = eh, meta.ew = ew, meta.C = C;
+  return ent_upload_tables(h, tables, K0 * (neighbours == 2 ? 9 : 3), ncum, meta);
+}
+
+}  // extern "C"
+
+namespace {
+// Validated tables into the handle's device buffer, K rows in the coder kernels' layout; meta: the
+// CRC and, version 3, what else the containers carry.
+int ent_upload_tables(tic_handle* h, const int64_t* tables, size_t K, size_t ncum, EntTables meta) {
   const size_t words = K * ncum;
   std::vector<uint32_t> host(words);
   for (size_t k = 0; k < K; ++k) {
@@ -912,17 +1331,24 @@ int tic_entropy_set_tables(tic_handle* h, const int64_t* tables, size_t K, size_
     t.d_tab = fresh;
     t.cap_words = words;
     std::lock_guard<std::mutex> lk(g_ent_mu);
-    g_ent[h].t = EntTables{fresh, words, 0, 0, 0};  // owned from here on; no tables until the copy is done
+    EntTables owned;  // owned from here on; no tables until the copy is done
+    owned.d_tab = fresh;
+    owned.cap_words = words;
+    g_ent[h].t = owned;
   }
   HIP_TRY(hipMemcpyAsync(t.d_tab, host.data(), words * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));  // `host` is free on return
-  t.K = (uint32_t)K;
-  t.ncum = (uint32_t)ncum;
-  t.crc = crc;
+  meta.d_tab = t.d_tab;
+  meta.cap_words = t.cap_words;
+  meta.K = (uint32_t)K;
+  meta.ncum = (uint32_t)ncum;
   std::lock_guard<std::mutex> lk(g_ent_mu);
-  g_ent[h].t = t;
+  g_ent[h].t = meta;
   return TIC_OK;
 }
+}  // namespace
+
+extern "C" {
 
 int tic_entropy_scratch_bytes(const int64_t* counts, int n_streams, uint32_t L, size_t* bytes) {
   if (!bytes) return fail(TIC_EINVAL, "null bytes");
@@ -941,28 +1367,28 @@ int tic_entropy_encode_device(tic_handle* h, const uint8_t* d_sym, const int64_t
                               int n_streams, uint32_t L, void* d_scratch, size_t scratch_bytes, uint8_t* d_out,
                               size_t out_cap, uint64_t* d_sizes) {
   return ent_encode(h, d_sym, sym_offsets, counts, n_streams, L, d_scratch, scratch_bytes, d_out, out_cap, d_sizes,
-                    false);
+                    1);
 }
 
 int tic_entropy_encode_ctx_device(tic_handle* h, const uint8_t* d_sym, const int64_t* sym_offsets,
                                   const int64_t* counts, int n_streams, uint32_t L, void* d_scratch,
                                   size_t scratch_bytes, uint8_t* d_out, size_t out_cap, uint64_t* d_sizes) {
   return ent_encode(h, d_sym, sym_offsets, counts, n_streams, L, d_scratch, scratch_bytes, d_out, out_cap, d_sizes,
-                    true);
+                    2);
 }
 
 int tic_entropy_decode_device(tic_handle* h, const uint8_t* d_blob, const int64_t* blob_offsets,
                               const int64_t* blob_sizes, const int64_t* counts, int n_streams, uint8_t* d_sym,
                               const int64_t* sym_offsets, void* d_scratch, size_t scratch_bytes) {
   return ent_decode(h, d_blob, blob_offsets, blob_sizes, counts, n_streams, d_sym, sym_offsets, d_scratch,
-                    scratch_bytes, false);
+                    scratch_bytes, 1);
 }
 
 int tic_entropy_decode_ctx_device(tic_handle* h, const uint8_t* d_blob, const int64_t* blob_offsets,
                                   const int64_t* blob_sizes, const int64_t* counts, int n_streams, uint8_t* d_sym,
                                   const int64_t* sym_offsets, void* d_scratch, size_t scratch_bytes) {
   return ent_decode(h, d_blob, blob_offsets, blob_sizes, counts, n_streams, d_sym, sym_offsets, d_scratch,
-                    scratch_bytes, true);
+                    scratch_bytes, 2);
 }
 
 int tic_histogram_ctx_device(tic_handle* h, const uint8_t* d_sym, size_t n, int Q, int K, uint64_t* d_counts) {
@@ -984,13 +1410,69 @@ int tic_histogram_ctx_device(tic_handle* h, const uint8_t* d_sym, size_t n, int 
   return check_launch();
 }
 
+int tic_entropy_encode_nbr_device(tic_handle* h, const uint8_t* d_sym, const int64_t* sym_offsets,
+                                  const int64_t* counts, int n_streams, uint32_t L, void* d_scratch,
+                                  size_t scratch_bytes, uint8_t* d_out, size_t out_cap, uint64_t* d_sizes) {
+  return ent_encode(h, d_sym, sym_offsets, counts, n_streams, L, d_scratch, scratch_bytes, d_out, out_cap, d_sizes,
+                    3);
+}
+
+int tic_entropy_decode_nbr_device(tic_handle* h, const uint8_t* d_blob, const int64_t* blob_offsets,
+                                  const int64_t* blob_sizes, const int64_t* counts, int n_streams, uint8_t* d_sym,
+                                  const int64_t* sym_offsets, void* d_scratch, size_t scratch_bytes) {
+  return ent_decode(h, d_blob, blob_offsets, blob_sizes, counts, n_streams, d_sym, sym_offsets, d_scratch,
+                    scratch_bytes, 3);
+}
+
+int tic_histogram_nbr_device(tic_handle* h, const uint8_t* d_sym, const int64_t* sym_offsets, const int64_t* counts,
+                             int n_streams, int Q, uint32_t L, uint64_t* d_counts) {
+  if (!h) return fail(TIC_EINVAL, "null handle");
+  if (Q < 1 || Q > 256) return fail(TIC_EINVAL, "Q %d must be in [1, 256]", Q);
+  if (n_streams < 0) return fail(TIC_EINVAL, "n_streams %d is negative", n_streams);
+  if (!ent_L_ok(L)) return fail(TIC_EINVAL, "segment length %u must be a multiple of 4 in [4, 16384]", L);
+  EntTables tb;
+  int rc = ent_tables(h, &tb, true);
+  if (rc) return rc;
+  if (n_streams == 0) return TIC_OK;
+  if (!d_sym || !d_counts) return fail(TIC_EINVAL, "null device pointer");
+  if (!sym_offsets || !counts) return fail(TIC_EINVAL, "null per-stream array");
+  if (((uintptr_t)d_counts & 7) != 0) return fail(TIC_EINVAL, "d_counts must be 8-byte aligned");
+  const char* why = "";
+  if (ent_segments(counts, n_streams, L, &why) < 0) return fail(TIC_EINVAL, "%s", why);
+  for (int i = 0; i < n_streams; ++i)
+    if (sym_offsets[i] < 0) return fail(TIC_EINVAL, "stream %d: negative offset %lld", i, (long long)sym_offsets[i]);
+  HIP_TRY(hipSetDevice(h->device));
+  const tic::EntNbr q = ent_nbr(tb);
+  for (int f = 0; f < n_streams; f += tic::kEntStreams) {
+    tic::EntChunk t;
+    memset(&t, 0, sizeof(t));
+    t.n = std::min(tic::kEntStreams, n_streams - f);
+    t.first = f;
+    long long most = 0;
+    for (int k = 0; k < t.n; ++k) {
+      t.in_off[k] = sym_offsets[f + k];
+      t.count[k] = counts[f + k];
+      most = std::max(most, (long long)counts[f + k]);
+    }
+    // pieces of 64 symbols, 256 to a workgroup
+    const unsigned gx = (unsigned)std::min<long long>((most / 64 + 256) / 256, (long long)h->num_cus * 8);
+    touch(h);
+    hipLaunchKernelGGL(tic::ent_histogram_nbr_kernel, dim3(gx, (unsigned)t.n), dim3(256), 0, h->stream, t, q, d_sym, Q,
+                       L, reinterpret_cast<unsigned long long*>(d_counts));
+    if ((rc = check_launch())) return rc;
+  }
+  return TIC_OK;
+}
+
 }  // extern "C"
 
 namespace {
 
 int ent_encode(tic_handle* h, const uint8_t* d_sym, const int64_t* sym_offsets, const int64_t* counts, int n_streams,
                uint32_t L, void* d_scratch, size_t scratch_bytes, uint8_t* d_out, size_t out_cap, uint64_t* d_sizes,
-               bool ctx) {
+               int ver) {
+  const bool ctx = ver >= 2, nbr = ver == 3;  // ctx: tables in the handle's buffer
+  const size_t hdr = nbr ? 36 : ctx ? 28 : 20;
   if (!h) return fail(TIC_EINVAL, "null handle");
   if (n_streams < 0) return fail(TIC_EINVAL, "n_streams %d is negative", n_streams);
   if (n_streams == 0) return TIC_OK;
@@ -1004,11 +1486,11 @@ int ent_encode(tic_handle* h, const uint8_t* d_sym, const int64_t* sym_offsets, 
   for (int i = 0; i < n_streams; ++i) {
     if (sym_offsets[i] < 0) return fail(TIC_EINVAL, "stream %d: negative offset %lld", i, (long long)sym_offsets[i]);
     const size_t S = ((size_t)counts[i] + L - 1) / L;
-    bound += (ctx ? 28 : 20) + 2 * S + 3 * (size_t)counts[i] + 4 * S;
+    bound += hdr + 2 * S + 3 * (size_t)counts[i] + 4 * S;
   }
   tic::EntModel m;
   EntTables tb;
-  int rc = ctx ? ent_tables(h, &tb) : ent_model(h, &m);
+  int rc = ctx ? ent_tables(h, &tb, nbr) : ent_model(h, &m);
   if (rc) return rc;
   if (((uintptr_t)d_scratch & 15) != 0 || ((uintptr_t)d_sizes & 7) != 0)
     return fail(TIC_EINVAL, "d_scratch must be 16-byte and d_sizes 8-byte aligned");
@@ -1016,15 +1498,18 @@ int ent_encode(tic_handle* h, const uint8_t* d_sym, const int64_t* sym_offsets, 
   if (scratch_bytes < need)
     return fail(TIC_EINVAL, "scratch of %zu bytes is too small (tic_entropy_scratch_bytes: %zu)", scratch_bytes, need);
   if (out_cap < bound)
-    return fail(TIC_EINVAL, "out_cap %zu is below the sum of tic_rcseg_bound%s (%zu)", out_cap, ctx ? "_ctx" : "",
+    return fail(TIC_EINVAL, "out_cap %zu is below the sum of tic_rcseg_bound%s (%zu)", out_cap, nbr ? "_nbr" : ctx ? "_ctx" : "",
                 bound);
   const size_t tab_bytes = ctx ? (size_t)tb.K * tb.ncum * sizeof(uint32_t) : 0;
   const bool in_lds = tab_bytes <= kEntLdsTables;
 
   HIP_TRY(hipSetDevice(h->device));
   if (ctx && in_lds && tab_bytes > 48 * 1024)
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(tic::ent_encode_ctx_kernel<1>),
+    HIP_TRY(hipFuncSetAttribute(nbr ? reinterpret_cast<const void*>(tic::ent_encode_nbr_kernel<1>)
+                                    : reinterpret_cast<const void*>(tic::ent_encode_ctx_kernel<1>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)tab_bytes));
+  const tic::EntNbr q = nbr ? ent_nbr(tb) : tic::EntNbr{};
+  const uint32_t g0 = nbr ? tb.eh | tb.ew << 16 : 0, g1 = nbr ? tb.C | tb.neighbours << 16 : 0;
   const EntScratch s = ent_carve(d_scratch, n_streams, T);
   long long segs = 0;
   for (int f = 0; f < n_streams; f += tic::kEntStreams) {
@@ -1050,6 +1535,12 @@ int ent_encode(tic_handle* h, const uint8_t* d_sym, const int64_t* sym_offsets, 
   if (!ctx)
     hipLaunchKernelGGL(tic::ent_encode_kernel, dim3(wgs), dim3(64), 0, h->stream, m, d_sym, rec, seg_base, n_streams,
                        L, s.slots, s.seg_len);
+  else if (nbr && in_lds)
+    hipLaunchKernelGGL(tic::ent_encode_nbr_kernel<1>, dim3(wgs), dim3(64), tab_bytes, h->stream,
+                       (const uint32_t*)tb.d_tab, q, d_sym, rec, seg_base, n_streams, L, s.slots, s.seg_len);
+  else if (nbr)
+    hipLaunchKernelGGL(tic::ent_encode_nbr_kernel<0>, dim3(wgs), dim3(64), 0, h->stream, (const uint32_t*)tb.d_tab, q,
+                       d_sym, rec, seg_base, n_streams, L, s.slots, s.seg_len);
   else if (in_lds)
     hipLaunchKernelGGL(tic::ent_encode_ctx_kernel<1>, dim3(wgs), dim3(64), tab_bytes, h->stream,
                        (const uint32_t*)tb.d_tab, tb.K, tb.ncum, d_sym, rec, seg_base, n_streams, L, s.slots,
@@ -1060,7 +1551,10 @@ int ent_encode(tic_handle* h, const uint8_t* d_sym, const int64_t* sym_offsets, 
   if ((rc = check_launch())) return rc;
   unsigned long long* sizes = reinterpret_cast<unsigned long long*>(d_sizes);
   const uint32_t* seg_len = s.seg_len;
-  if (ctx)
+  if (nbr)
+    hipLaunchKernelGGL(tic::ent_seg_scan_kernel<36>, dim3((unsigned)n_streams), dim3(256), 0, h->stream, rec, seg_base,
+                       seg_len, s.seg_off, sizes);
+  else if (ctx)
     hipLaunchKernelGGL(tic::ent_seg_scan_kernel<28>, dim3((unsigned)n_streams), dim3(256), 0, h->stream, rec, seg_base,
                        seg_len, s.seg_off, sizes);
   else
@@ -1072,18 +1566,22 @@ int ent_encode(tic_handle* h, const uint8_t* d_sym, const int64_t* sym_offsets, 
   if ((rc = check_launch())) return rc;
   const uint8_t* slots = s.slots;
   const unsigned long long *seg_off = s.seg_off, *csizes = sizes, *out_off = s.aux;
-  if (ctx)
+  if (nbr)
+    hipLaunchKernelGGL(tic::ent_gather_kernel<36>, dim3((unsigned)T), dim3(256), 0, h->stream, rec, seg_base,
+                       n_streams, L, slots, seg_len, seg_off, csizes, out_off, tb.K0, tb.crc, g0, g1, d_out);
+  else if (ctx)
     hipLaunchKernelGGL(tic::ent_gather_kernel<28>, dim3((unsigned)T), dim3(256), 0, h->stream, rec, seg_base,
-                       n_streams, L, slots, seg_len, seg_off, csizes, out_off, tb.K, tb.crc, d_out);
+                       n_streams, L, slots, seg_len, seg_off, csizes, out_off, tb.K, tb.crc, 0u, 0u, d_out);
   else
     hipLaunchKernelGGL(tic::ent_gather_kernel<20>, dim3((unsigned)T), dim3(256), 0, h->stream, rec, seg_base,
-                       n_streams, L, slots, seg_len, seg_off, csizes, out_off, 0u, 0u, d_out);
+                       n_streams, L, slots, seg_len, seg_off, csizes, out_off, 0u, 0u, 0u, 0u, d_out);
   return check_launch();
 }
 
 int ent_decode(tic_handle* h, const uint8_t* d_blob, const int64_t* blob_offsets, const int64_t* blob_sizes,
                const int64_t* counts, int n_streams, uint8_t* d_sym, const int64_t* sym_offsets, void* d_scratch,
-               size_t scratch_bytes, bool ctx) {
+               size_t scratch_bytes, int ver) {
+  const bool ctx = ver >= 2, nbr = ver == 3;
   if (!h) return fail(TIC_EINVAL, "null handle");
   if (n_streams < 0) return fail(TIC_EINVAL, "n_streams %d is negative", n_streams);
   if (n_streams == 0) return TIC_OK;
@@ -1097,7 +1595,7 @@ int ent_decode(tic_handle* h, const uint8_t* d_blob, const int64_t* blob_offsets
       return fail(TIC_EINVAL, "stream %d: negative offset or size", i);
   tic::EntModel m;
   EntTables tb;
-  int rc = ctx ? ent_tables(h, &tb) : ent_model(h, &m);
+  int rc = ctx ? ent_tables(h, &tb, nbr) : ent_model(h, &m);
   if (rc) return rc;
   if (((uintptr_t)d_scratch & 15) != 0) return fail(TIC_EINVAL, "d_scratch must be 16-byte aligned");
   const size_t fixed = ent_fixed(n_streams);
@@ -1110,11 +1608,22 @@ int ent_decode(tic_handle* h, const uint8_t* d_blob, const int64_t* blob_offsets
   const int lut = !ctx && total <= tic::kEntLutMax;
   const size_t tab_bytes = ctx ? (size_t)tb.K * tb.ncum * sizeof(uint32_t) : 0;
   const bool in_lds = tab_bytes <= kEntLdsTables;
-  const size_t lds = ctx ? (in_lds ? tab_bytes : 0) : 260 * sizeof(uint32_t) + (lut ? ((size_t)total + 3) / 4 * 4 : 0);
+  const tic::EntNbr q = nbr ? ent_nbr(tb) : tic::EntNbr{};
+  const uint32_t g0 = nbr ? tb.eh | tb.ew << 16 : 0, g1 = nbr ? tb.C | tb.neighbours << 16 : 0;
+  // version 3: a lane's ring of class bits, whole words, for each of a workgroup's 64 lanes
+  const size_t ring_bytes = nbr ? ((size_t)q.ring + 31) / 32 * 4 * 64 : 0;
+  const bool ring = ring_bytes <= kEntLdsRings;
+  const size_t lds = ctx ? (in_lds ? tab_bytes : 0) + (ring ? ring_bytes : 0)
+                         : 260 * sizeof(uint32_t) + (lut ? ((size_t)total + 3) / 4 * 4 : 0);
+  const void* dec_nbr = in_lds ? (ring ? reinterpret_cast<const void*>(tic::ent_decode_nbr_kernel<1, 1>)
+                                       : reinterpret_cast<const void*>(tic::ent_decode_nbr_kernel<1, 0>))
+                               : (ring ? reinterpret_cast<const void*>(tic::ent_decode_nbr_kernel<0, 1>)
+                                       : reinterpret_cast<const void*>(tic::ent_decode_nbr_kernel<0, 0>));
   HIP_TRY(hipSetDevice(h->device));
   if (lds > 48 * 1024)
-    HIP_TRY(hipFuncSetAttribute(ctx ? reinterpret_cast<const void*>(tic::ent_decode_ctx_kernel<1>)
-                                    : reinterpret_cast<const void*>(tic::ent_decode_kernel),
+    HIP_TRY(hipFuncSetAttribute(nbr   ? dec_nbr
+                                : ctx ? reinterpret_cast<const void*>(tic::ent_decode_ctx_kernel<1>)
+                                      : reinterpret_cast<const void*>(tic::ent_decode_kernel),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   const EntScratch s = ent_carve(d_scratch, n_streams, 0);
   for (int f = 0; f < n_streams; f += tic::kEntStreams) {
@@ -1129,19 +1638,25 @@ int ent_decode(tic_handle* h, const uint8_t* d_blob, const int64_t* blob_offsets
       t.out_off[k] = sym_offsets[f + k];
     }
     touch(h);
-    if (ctx)
-      hipLaunchKernelGGL(tic::ent_dec_header_kernel<28>, dim3(1), dim3(64), 0, h->stream, t, d_blob, tb.K, tb.crc,
-                         s.rec, s.aux);
+    if (nbr)
+      hipLaunchKernelGGL(tic::ent_dec_header_kernel<36>, dim3(1), dim3(64), 0, h->stream, t, d_blob, tb.K0, tb.crc, g0,
+                         g1, s.rec, s.aux);
+    else if (ctx)
+      hipLaunchKernelGGL(tic::ent_dec_header_kernel<28>, dim3(1), dim3(64), 0, h->stream, t, d_blob, tb.K, tb.crc, 0u,
+                         0u, s.rec, s.aux);
     else
-      hipLaunchKernelGGL(tic::ent_dec_header_kernel<20>, dim3(1), dim3(64), 0, h->stream, t, d_blob, 0u, 0u, s.rec,
-                         s.aux);
+      hipLaunchKernelGGL(tic::ent_dec_header_kernel<20>, dim3(1), dim3(64), 0, h->stream, t, d_blob, 0u, 0u, 0u, 0u,
+                         s.rec, s.aux);
     if ((rc = check_launch())) return rc;
   }
   hipLaunchKernelGGL(tic::ent_stream_scan_kernel, dim3(1), dim3(256), 0, h->stream, (const unsigned long long*)s.aux,
                      n_streams, s.seg_base);
   if ((rc = check_launch())) return rc;
   const unsigned long long* seg_base = s.seg_base;
-  if (ctx)
+  if (nbr)
+    hipLaunchKernelGGL(tic::ent_dec_scan_kernel<36>, dim3((unsigned)n_streams), dim3(256), 0, h->stream, d_blob, s.rec,
+                       seg_base, cap, s.seg_off, d_sym);
+  else if (ctx)
     hipLaunchKernelGGL(tic::ent_dec_scan_kernel<28>, dim3((unsigned)n_streams), dim3(256), 0, h->stream, d_blob, s.rec,
                        seg_base, cap, s.seg_off, d_sym);
   else
@@ -1154,6 +1669,18 @@ int ent_decode(tic_handle* h, const uint8_t* d_blob, const int64_t* blob_offsets
   if (!ctx)
     hipLaunchKernelGGL(tic::ent_decode_kernel, dim3(wgs), dim3(64), lds, h->stream, m, lut, d_blob, rec, seg_base,
                        n_streams, seg_off, d_sym);
+  else if (nbr && in_lds && ring)
+    hipLaunchKernelGGL((tic::ent_decode_nbr_kernel<1, 1>), dim3(wgs), dim3(64), lds, h->stream,
+                       (const uint32_t*)tb.d_tab, q, d_blob, rec, seg_base, n_streams, seg_off, d_sym);
+  else if (nbr && in_lds)
+    hipLaunchKernelGGL((tic::ent_decode_nbr_kernel<1, 0>), dim3(wgs), dim3(64), lds, h->stream,
+                       (const uint32_t*)tb.d_tab, q, d_blob, rec, seg_base, n_streams, seg_off, d_sym);
+  else if (nbr && ring)
+    hipLaunchKernelGGL((tic::ent_decode_nbr_kernel<0, 1>), dim3(wgs), dim3(64), lds, h->stream,
+                       (const uint32_t*)tb.d_tab, q, d_blob, rec, seg_base, n_streams, seg_off, d_sym);
+  else if (nbr)
+    hipLaunchKernelGGL((tic::ent_decode_nbr_kernel<0, 0>), dim3(wgs), dim3(64), lds, h->stream,
+                       (const uint32_t*)tb.d_tab, q, d_blob, rec, seg_base, n_streams, seg_off, d_sym);
   else if (in_lds)
     hipLaunchKernelGGL(tic::ent_decode_ctx_kernel<1>, dim3(wgs), dim3(64), lds, h->stream, (const uint32_t*)tb.d_tab,
                        tb.K, tb.ncum, d_blob, rec, seg_base, n_streams, seg_off, d_sym);

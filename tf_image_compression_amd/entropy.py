@@ -1,4 +1,4 @@
-"""Segmented range-coder streams ("TICS" versions 1 and 2, include/tic.h), host side.
+"""Segmented range-coder streams ("TICS" versions 1 to 3, include/tic.h), host side.
 
 A container cuts a symbol sequence into segments of ``L`` symbols, each an independent stream of
 the range coder in csrc/range_coder.cpp (byte for byte what ``RangeEncoder`` writes for the
@@ -13,6 +13,12 @@ A 2-D table ``[K, ncum]`` selects the periodic context model of version 2: symbo
 stream is coded under row ``k mod K`` (``K`` = the code's channel count: one table per channel;
 ``K`` = the symbols of a patch: one per code position).  ``pack``, ``unpack`` and ``bound`` take
 either kind of table; ``parse`` reads version 1 only and ``parse_ctx`` version 2 only.
+
+A 3-D table ``[K0, M, ncum]`` selects the causal-neighbour model of version 3 and needs
+``geometry=(eh, ew, C)``, the shape of the code the symbols are a patch-major sequence of:
+``M`` = 3 conditions every symbol on the class of its W neighbour (one position to the left, same
+channel), ``M`` = 9 on W and N (one row up); symbol ``k`` is coded under row ``k mod K0`` of the
+tables, entry ``nb`` (include/tic.h has the definition).  ``parse_nbr`` reads version 3 only.
 """
 from __future__ import annotations
 
@@ -26,6 +32,7 @@ from .range_coder import _raise, _table
 MAGIC = b"TICS"
 HEADER_BYTES = 20
 HEADER_BYTES_CTX = 28
+HEADER_BYTES_NBR = 36
 DEFAULT_SEGMENT = 2048  # faster than 4096 end to end, under 1 % bytes over the single stream
 
 
@@ -59,11 +66,46 @@ def container_version(buf) -> int:
 
 
 def is_ctx_table(cum_freq) -> bool:
-    """True for a 2-D ``[K, ncum]`` table (version 2), False for a 1-D one (version 1)."""
+    """True for a 2-D ``[K, ncum]`` table (version 2), False for a 1-D one (version 1) and for a
+    3-D one (version 3, ``is_nbr_table``)."""
     try:
-        return len(cum_freq) > 0 and np.ndim(cum_freq[0]) > 0
+        return len(cum_freq) > 0 and np.ndim(cum_freq[0]) > 0 and not is_nbr_table(cum_freq)
     except TypeError:
         return False
+
+
+def is_nbr_table(cum_freq) -> bool:
+    """True for a 3-D ``[K0, M, ncum]`` table (version 3)."""
+    try:
+        return len(cum_freq) > 0 and np.ndim(cum_freq[0]) > 1
+    except TypeError:
+        return False
+
+
+def nbr_tables(tables) -> np.ndarray:
+    """``[K0, M, ncum]`` cumulative tables as a C-contiguous int64 array; ``M`` is 3 (W) or 9
+    (W and N)."""
+    rows = [ctx_tables(block) for block in tables]
+    if not rows or len({r.shape for r in rows}) != 1:
+        raise ValueError("neighbour tables need at least one context and one common shape")
+    t = np.ascontiguousarray(np.stack(rows))
+    if t.shape[1] not in (3, 9):
+        raise ValueError(f"neighbour tables are [K0, 3 or 9, ncum], got shape {t.shape}")
+    return t
+
+
+def neighbours_of(tables) -> int:
+    """1 for ``[K0, 3, ncum]`` tables, 2 for ``[K0, 9, ncum]``."""
+    return {3: 1, 9: 2}[nbr_tables(tables).shape[1]]
+
+
+def _geometry(geometry):
+    if geometry is None:
+        raise ValueError("3-D (neighbour) tables need geometry=(eh, ew, C)")
+    eh, ew, c = (int(v) for v in geometry)
+    if not all(1 <= v <= 65535 for v in (eh, ew, c)):
+        raise ValueError(f"code geometry {eh} x {ew} x {c} must be in [1, 65535] each")
+    return eh, ew, c
 
 
 def ctx_tables(tables) -> np.ndarray:
@@ -76,31 +118,43 @@ def ctx_tables(tables) -> np.ndarray:
 
 
 def tables_crc(tables) -> int:
-    """The CRC-32C a version-2 header carries: of the ``K * ncum`` entries as little-endian
-    int64, row-major."""
-    data = ctx_tables(tables).astype("<i8").tobytes()
+    """The CRC-32C a version-2 or version-3 header carries: of the ``K * ncum`` entries (2-D or
+    3-D tables) as little-endian int64, row-major."""
+    t = nbr_tables(tables) if is_nbr_table(tables) else ctx_tables(tables)
+    data = t.astype("<i8").tobytes()
     return int(lib().tic_crc32c(data, len(data), 0))
 
 
 def bound(n: int, segment: int = DEFAULT_SEGMENT, cum_freq=None) -> int:
-    """Worst-case container size for ``n`` symbols (version 2 when ``cum_freq`` is 2-D)."""
+    """Worst-case container size for ``n`` symbols (version 2 when ``cum_freq`` is 2-D, version 3
+    when it is 3-D)."""
     out = C.c_size_t()
-    fn = lib().tic_rcseg_bound_ctx if cum_freq is not None and is_ctx_table(cum_freq) else lib().tic_rcseg_bound
+    fn = lib().tic_rcseg_bound
+    if cum_freq is not None and is_nbr_table(cum_freq):
+        fn = lib().tic_rcseg_bound_nbr
+    elif cum_freq is not None and is_ctx_table(cum_freq):
+        fn = lib().tic_rcseg_bound_ctx
     rc = fn(int(n), int(segment), C.byref(out))
     if rc:
         _raise(rc, "entropy.bound")
     return int(out.value)
 
 
-def pack(symbols, cum_freq, segment: int = DEFAULT_SEGMENT) -> bytes:
-    """The container of ``symbols`` (flattened in C order); version 2 under a 2-D table."""
-    ctx = is_ctx_table(cum_freq)
-    table = ctx_tables(cum_freq) if ctx else _table(cum_freq)
+def pack(symbols, cum_freq, segment: int = DEFAULT_SEGMENT, geometry=None) -> bytes:
+    """The container of ``symbols`` (flattened in C order); version 2 under a 2-D table, version 3
+    under a 3-D one (with ``geometry``)."""
+    ctx, nbr = is_ctx_table(cum_freq), is_nbr_table(cum_freq)
+    table = nbr_tables(cum_freq) if nbr else ctx_tables(cum_freq) if ctx else _table(cum_freq)
     sym = _symbols(symbols)
     cap = bound(sym.size, segment, cum_freq)
     out = np.empty(cap, np.uint8)
     written = C.c_size_t()
-    if ctx:
+    if nbr:
+        eh, ew, c = _geometry(geometry)
+        rc = lib().tic_rcseg_encode_nbr(_u8(sym), sym.size, int(segment), _i64(table), table.shape[0],
+                                        neighbours_of(table), table.shape[2], eh, ew, c, _u8(out), cap,
+                                        C.byref(written))
+    elif ctx:
         rc = lib().tic_rcseg_encode_ctx(_u8(sym), sym.size, int(segment), _i64(table), table.shape[0],
                                         table.shape[1], _u8(out), cap, C.byref(written))
     else:
@@ -132,16 +186,34 @@ def parse_ctx(buf) -> tuple[int, int, int, int]:
     return int(L.value), int(n.value), int(K.value), int(crc.value)
 
 
-def unpack(buf, cum_freq, n: int | None = None) -> np.ndarray:
+def parse_nbr(buf) -> tuple[int, int, int, int, tuple[int, int, int], int]:
+    """Validate a version-3 container; ``(L, n, K0, crc, (eh, ew, C), neighbours)``."""
+    a = np.frombuffer(bytes(buf), np.uint8)
+    L, n = C.c_uint32(), C.c_uint64()
+    f = [C.c_uint32() for _ in range(6)]
+    rc = lib().tic_rcseg_parse_nbr(_u8(a) if a.size else None, a.size, C.byref(L), C.byref(n),
+                                   *[C.byref(v) for v in f])
+    if rc:
+        _raise(rc, "entropy.parse_nbr")
+    K0, crc, eh, ew, c, nb = (int(v.value) for v in f)
+    return int(L.value), int(n.value), K0, crc, (eh, ew, c), nb
+
+
+def unpack(buf, cum_freq, n: int | None = None, geometry=None) -> np.ndarray:
     """The symbols of a container (uint8); ``n``, when given, must be the header's count.  A 2-D
-    table reads version 2 and must be the one the container was packed under (its K and CRC)."""
-    ctx = is_ctx_table(cum_freq)
-    table = ctx_tables(cum_freq) if ctx else _table(cum_freq)
+    table reads version 2 and must be the one the container was packed under (its K and CRC); a
+    3-D table reads version 3 and must match its K0, ``neighbours``, CRC and ``geometry``."""
+    ctx, nbr = is_ctx_table(cum_freq), is_nbr_table(cum_freq)
+    table = nbr_tables(cum_freq) if nbr else ctx_tables(cum_freq) if ctx else _table(cum_freq)
     a = np.frombuffer(bytes(buf), np.uint8)
     if n is None:
-        n = parse_ctx(a)[1] if ctx else parse(a)[1]
+        n = parse_nbr(a)[1] if nbr else parse_ctx(a)[1] if ctx else parse(a)[1]
     out = np.empty(int(n), np.uint8)
-    if ctx:
+    if nbr:
+        eh, ew, c = _geometry(geometry)
+        rc = lib().tic_rcseg_decode_nbr(_u8(a) if a.size else None, a.size, _i64(table), table.shape[0],
+                                        neighbours_of(table), table.shape[2], eh, ew, c, _u8(out), int(n))
+    elif ctx:
         rc = lib().tic_rcseg_decode_ctx(_u8(a) if a.size else None, a.size, _i64(table), table.shape[0],
                                         table.shape[1], _u8(out), int(n))
     else:

@@ -319,11 +319,14 @@ class ImageCodec:
     # host, every image becomes one "TICS" container (entropy.py), all of them in one coder call.
     def _entropy_encode(self, d_sym: DeviceBuffer, counts, cum_freq, segment: int):
         """Symbols of consecutive streams in ``d_sym`` -> (d_blob, d_sizes), nothing downloaded.
-        A 2-D ``cum_freq`` ([K, ncum], entropy.py) takes the context coder: version-2 containers."""
+        A 2-D ``cum_freq`` ([K, ncum], entropy.py) takes the context coder: version-2 containers; a
+        3-D one ([K0, M, ncum]) the neighbour coder under the codec's code shape: version 3."""
         from . import entropy
         c = self.codec
-        ctx = entropy.is_ctx_table(cum_freq)
-        if ctx:
+        ctx, nbr = entropy.is_ctx_table(cum_freq), entropy.is_nbr_table(cum_freq)
+        if nbr:
+            c.entropy_set_tables_nbr(cum_freq)
+        elif ctx:
             c.entropy_set_tables(cum_freq)
         else:
             c.entropy_set_table(cum_freq)
@@ -331,7 +334,7 @@ class ImageCodec:
         d_scr = self._buf("entropy_scratch", c.entropy_scratch_bytes(counts, segment))
         d_blob = self._buf("entropy_blob", sum(entropy.bound(n, segment, cum_freq) for n in counts))
         d_sizes = self._buf("entropy_sizes", 8 * len(counts))
-        encode = c.entropy_encode_ctx_device if ctx else c.entropy_encode_device
+        encode = c.entropy_encode_nbr_device if nbr else c.entropy_encode_ctx_device if ctx else c.entropy_encode_device
         encode(d_sym, offs, counts, segment, d_scr, d_blob, d_sizes)
         return d_blob, d_sizes
 
@@ -339,7 +342,9 @@ class ImageCodec:
         """[uint8 [H_i, W_i, 3]] -> one segmented-stream container per image (entropy.unpack gives
         ``encode_images``' symbols back): one upload, ``encode_images_device``, one coder call over
         all images, one download of the sizes and one of the containers.  A 2-D ``cum_freq``
-        ([K, ncum]) codes symbol k of an image under row k mod K and writes version-2 containers."""
+        ([K, ncum]) codes symbol k of an image under row k mod K and writes version-2 containers; a
+        3-D one ([K0, M, ncum]) also conditions on the causal neighbours' classes (version 3, the
+        geometry being this codec's code shape)."""
         imgs = [np.ascontiguousarray(im) for im in images]
         for im in imgs:
             if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3 or im.size == 0:
@@ -367,10 +372,15 @@ class ImageCodec:
         """[container], [(H_i, W_i)] -> [uint8 [H_i, W_i, 3]]: every container is validated on the
         host (entropy.parse) and its symbol count checked against the image size and the code
         shape; then one upload, one decoder call for all of them and ``decode_images_device``.  A 2-D
-        ``cum_freq`` reads version-2 containers, which must have been coded under these tables."""
+        ``cum_freq`` reads version-2 containers, which must have been coded under these tables; a
+        3-D one version-3 containers coded under these tables for this codec's code shape."""
         from . import entropy
-        ctx = entropy.is_ctx_table(cum_freq)
-        if ctx:
+        ctx, nbr = entropy.is_ctx_table(cum_freq), entropy.is_nbr_table(cum_freq)
+        if nbr:
+            tables = entropy.nbr_tables(cum_freq)
+            crc = entropy.tables_crc(tables)
+            mine = (tables.shape[0], tuple(int(v) for v in self.codec.code_shape), entropy.neighbours_of(tables))
+        elif ctx:
             tables = entropy.ctx_tables(cum_freq)
             crc = entropy.tables_crc(tables)
         sizes = [(int(H), int(W)) for H, W in sizes]
@@ -384,7 +394,13 @@ class ImageCodec:
         for i, (buf, (H, W)) in enumerate(zip(streams, sizes)):
             if H <= 0 or W <= 0:
                 raise ValueError(f"image size {H}x{W} must be positive")
-            if ctx:
+            if nbr:
+                L, n, K0, hcrc, geometry, neighbours = entropy.parse_nbr(buf)
+                if (K0, geometry, neighbours) != mine or hcrc != crc:
+                    raise ValueError(f"stream {i} was coded under other neighbour tables (K0 {K0}, geometry "
+                                     f"{geometry}, neighbours {neighbours}, CRC {hcrc:#010x}; given K0 {mine[0]}, "
+                                     f"geometry {mine[1]}, neighbours {mine[2]}, CRC {crc:#010x})")
+            elif ctx:
                 L, n, K, hcrc = entropy.parse_ctx(buf)
                 if K != tables.shape[0] or hcrc != crc:
                     raise ValueError(f"stream {i} was coded under other context tables (K {K}, CRC {hcrc:#010x}; "
@@ -400,7 +416,9 @@ class ImageCodec:
         bsizes = [len(b) for b in streams]
         boffs = np.concatenate([[0], np.cumsum(bsizes)[:-1]]).astype(np.int64)
         soffs = np.concatenate([[0], np.cumsum(counts)[:-1]]).astype(np.int64)
-        if ctx:
+        if nbr:
+            c.entropy_set_tables_nbr(tables)
+        elif ctx:
             c.entropy_set_tables(tables)
         else:
             c.entropy_set_table(cum_freq)
@@ -408,7 +426,7 @@ class ImageCodec:
         d_blob.upload(blob)
         d_scr = self._buf("entropy_scratch", c.entropy_scratch_bytes(counts, min_L))
         d_sym = self._buf("symbols", sum(counts))
-        decode = c.entropy_decode_ctx_device if ctx else c.entropy_decode_device
+        decode = c.entropy_decode_nbr_device if nbr else c.entropy_decode_ctx_device if ctx else c.entropy_decode_device
         decode(d_blob, boffs, bsizes, counts, d_sym, soffs, d_scr)
         offsets, total = self.packed_offsets(sizes)
         d_out = self._buf("image_out", total)
@@ -433,11 +451,18 @@ class ImageCodec:
         from one entropy_encode_device call over the symbols on the device (the real rate beside
         the estimate).  Under a 2-D ``cum_freq`` ([K, Q + 1] context tables, entropy.py)
         ``est_bits`` is evaluate.estimated_bits_ctx of the image's per-context histogram
-        (tic_histogram_ctx_device) and ``coded_bytes`` the size of its version-2 container.  Images
+        (tic_histogram_ctx_device) and ``coded_bytes`` the size of its version-2 container; under a
+        3-D one ([K0, M, Q + 1]) ``est_bits`` uses the rows the neighbour coder uses at
+        ``entropy_segment`` (tic_histogram_nbr_device; entropy.DEFAULT_SEGMENT without one) and
+        ``coded_bytes`` is the size of the version-3 container.  Images
         start at 4-byte boundaries of the arena (the alignment tic_sse_u8_device asks for)."""
         from . import entropy
         from . import evaluate as ev
         tables = entropy.ctx_tables(cum_freq) if cum_freq is not None and entropy.is_ctx_table(cum_freq) else None
+        nbr = cum_freq is not None and entropy.is_nbr_table(cum_freq)
+        if nbr:  # the estimate sees the K0 * M rows as a version-2 estimate sees its K rows
+            t3 = entropy.nbr_tables(cum_freq)
+            tables = t3.reshape(-1, t3.shape[2])
         imgs = [np.ascontiguousarray(im) for im in images]
         for im in imgs:
             if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3 or im.size == 0:
@@ -488,9 +513,16 @@ class ImageCodec:
                 raise ValueError(f"context tables of {tables.shape[1] - 1} symbols for a quantiser of {Q}")
             d_ctx = self._buf("eval_ctx_counts", n * K * Q * 8)
             c.memset_device(d_ctx, 0, n * K * Q * 8)
+            if nbr:
+                c.entropy_set_tables_nbr(t3)
+                seg = entropy.DEFAULT_SEGMENT if entropy_segment is None else int(entropy_segment)
             for i in range(n):
-                c.histogram_ctx_device(d_sym.view(int(pbase[i]) * code), counts[i] * code, Q, K,
-                                       d_ctx.view(i * K * Q * 8))
+                if nbr:
+                    c.histogram_nbr_device(d_sym, [int(pbase[i]) * code], [counts[i] * code], Q, seg,
+                                           d_ctx.view(i * K * Q * 8))
+                else:
+                    c.histogram_ctx_device(d_sym.view(int(pbase[i]) * code), counts[i] * code, Q, K,
+                                           d_ctx.view(i * K * Q * 8))
             ctx_counts = d_ctx.download((n, K, Q), np.uint64)
         raw = d_res.download((n * rec + len(big) * 240,), np.uint8)
         ints = raw[:n * rec].view(np.uint64).reshape(n, 1 + Q)

@@ -167,17 +167,27 @@ def symbol_table(prob, resolution=4096):
 
 
 def dist_is_ctx(path) -> bool:
-    """True when the distribution file at ``path`` holds a 2-D ``[K, Q]`` array (the per-context
-    probabilities get_encoded_distribution.py --context writes); False for the 1-D table or a
-    missing file."""
+    """True when the distribution file at ``path`` holds a 2-D ``[K, Q]`` or a 3-D ``[K0, M, Q]``
+    array (the per-context probabilities get_encoded_distribution.py --context [--neighbours]
+    writes); False for the 1-D table or a missing file."""
     if not os.path.exists(path):
         return False
-    return np.load(path, mmap_mode="r", allow_pickle=False).ndim == 2
+    return np.load(path, mmap_mode="r", allow_pickle=False).ndim >= 2
+
+
+def dist_ndim(path) -> int:
+    """Dimensions of the distribution array at ``path``: 1 (one table), 2 (``[K, Q]``, per-context)
+    or 3 (``[K0, M, Q]``, context x causal neighbours); 0 for a missing file."""
+    if not os.path.exists(path):
+        return 0
+    return int(np.load(path, mmap_mode="r", allow_pickle=False).ndim)
 
 
 def dist_table(prob, resolution=4096):
     """The coder's table(s) of a distribution array: ``symbol_table`` of a 1-D one,
-    ``symbol_tables`` of a 2-D one."""
+    ``symbol_tables`` of a 2-D one, ``symbol_tables_nbr`` of a 3-D one."""
+    if np.ndim(prob) == 3:
+        return symbol_tables_nbr(prob, resolution)
     return symbol_tables(prob, resolution) if np.ndim(prob) == 2 else symbol_table(prob, resolution)
 
 
@@ -188,3 +198,26 @@ def symbol_tables(prob, resolution=4096):
     if p.ndim != 2 or p.shape[0] == 0:
         raise ValueError(f"context probabilities must be [K, Q], got shape {p.shape}")
     return np.array([symbol_table(row, resolution=resolution) for row in p], dtype=np.int64)
+
+
+def symbol_tables_nbr(prob, resolution=4096):
+    """``symbol_table`` of every row of ``prob[K0, M, Q]`` (``M`` = 3 or 9): the ``[K0, M, Q + 1]``
+    tables of the causal-neighbour model (entropy.py, "TICS" version 3), as an int64 array."""
+    p = np.asarray(prob, np.float64)
+    if p.ndim != 3 or p.shape[0] == 0 or p.shape[1] not in (3, 9):
+        raise ValueError(f"neighbour probabilities must be [K0, 3 or 9, Q], got shape {p.shape}")
+    return symbol_tables(p.reshape(-1, p.shape[2]), resolution).reshape(p.shape[0], p.shape[1], p.shape[2] + 1)
+
+
+def nbr_probabilities(counts):
+    """Probabilities ``[K0, M, Q]`` from the counts of a causal-neighbour histogram.  A context
+    never seen backs off to its row's distribution summed over ``nb`` (uniform when the whole row
+    is empty), and every seen context is smoothed by one count of that distribution, so no entry
+    is zero."""
+    c = np.asarray(counts, np.float64)
+    if c.ndim != 3:
+        raise ValueError(f"neighbour counts must be [K0, M, Q], got shape {c.shape}")
+    back = c.sum(axis=1, keepdims=True) + 1.0 / c.shape[2]  # never zero
+    back = back / back.sum(axis=2, keepdims=True)
+    c = c + back
+    return c / c.sum(axis=2, keepdims=True)
