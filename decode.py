@@ -9,6 +9,8 @@ parsing), :143-264 (uncompress).  ``-g`` accepts -1..7 (-1 is accepted for
 compatibility; there is no CPU path, so it maps to device 0 with a warning).
 ``--entropy device`` reads the segmented-stream containers ``encode.py --entropy device``
 writes and decodes them on the GPU, a group of files per call.
+``--region X,Y,W,H`` (with ``--entropy device``) writes only that rectangle of every image,
+``<stem>_x{X}_y{Y}_{W}x{H}.png``, decoded from the patches and the container segments it needs.
 """
 import argparse
 import os
@@ -45,7 +47,25 @@ def my_parse_args(argv=None):
     p.add_argument("--entropy", choices=["host", "device"], default="host",
                    help="host: single-stream files (the default); device: segmented-stream containers "
                         "(encode.py --entropy device), range-decoded on the GPU")
+    p.add_argument("--region", type=str, default="", metavar="X,Y,W,H",
+                   help="decode only the W x H rectangle at column X, row Y of every image (needs --entropy "
+                        "device): the bytes of that crop of the full decode, written as "
+                        "<stem>_x{X}_y{Y}_{W}x{H}.png")
     args = p.parse_args(argv)
+    if args.region:
+        if args.raw:
+            p.error("--region reads segmented streams: it cannot be combined with --raw")
+        if args.entropy != "device":
+            p.error("--region needs --entropy device: the single-stream host coder cannot start inside a stream")
+        try:
+            x, y, w, h = (int(v) for v in args.region.split(","))
+        except ValueError:
+            p.error(f"--region {args.region!r} is not X,Y,W,H (four integers)")
+        if x < 0 or y < 0 or w <= 0 or h <= 0:
+            p.error(f"--region {args.region!r}: X and Y must not be negative, W and H must be positive")
+        args.region = (x, y, w, h)
+    else:
+        args.region = None
     if args.entropy == "device" and args.raw:
         p.error("--raw files hold no entropy-coded stream: it cannot be combined with --entropy device")
     if args.entropy == "host" and not args.raw:
@@ -65,6 +85,9 @@ def get_img_info(filename, config):
 
 def get_recons_image_path(filename, args, config):
     stem = filename.replace(".encoded", "").split(config["name_sep"])[0]
+    if getattr(args, "region", None):
+        x, y, w, h = args.region
+        stem += f"_x{x}_y{y}_{w}x{h}"
     return str(Path(args.output_dir.format(args.model_num)) / (stem + ".png"))
 
 
@@ -180,13 +203,25 @@ def uncompress(model, args):
         # groups as for --batch-images; every container is validated on the host (tic_rcseg_parse),
         # then the group's containers are decoded on the GPU in one call
         sizes = [get_img_info(f, config)[1:] for f in filenames]
+        region = None
+        if args.region:
+            x, y, w, h = args.region
+            region = (y, x, h, w)
+            for f, (height, width) in zip(filenames, sizes):
+                if y + h > height or x + w > width:
+                    raise ValueError(f"{Path(input_dir) / f}: the image is {width} x {height}, it does not contain "
+                                     f"the region {w} x {h} at ({x}, {y})")
         for group in ic.plan_batches(sizes, P, args.batch_images):
             streams = [(Path(input_dir) / filenames[i]).read_bytes() for i in group]
             for i, stream in zip(group, streams):
                 check_container_version(str(Path(input_dir) / filenames[i]), stream, cum_freq, args,
                                         ic.codec.code_shape)
-            images = ic.decode_streams_to_images(streams, [sizes[i] for i in group], cum_freq,
-                                                 post_filter=post is not None)
+            if region:
+                images = ic.decode_regions(streams, [sizes[i] for i in group], [region] * len(group), cum_freq,
+                                           post_filter=post is not None)
+            else:
+                images = ic.decode_streams_to_images(streams, [sizes[i] for i in group], cum_freq,
+                                                     post_filter=post is not None)
             for i, recons in zip(group, images):
                 store(filenames[i], recons)
     elif args.batch_images == 1:

@@ -430,6 +430,35 @@ int tic_rcseg_parse_nbr(const uint8_t* buf, size_t nbytes, uint32_t* L, uint64_t
 int tic_rcseg_decode_nbr(const uint8_t* buf, size_t nbytes, const int64_t* tables, size_t K0, uint32_t neighbours,
                          size_t ncum, uint32_t eh, uint32_t ew, uint32_t C, uint8_t* sym_out, size_t n);
 
+/* --- symbol ranges of a segmented stream (host part) ---
+ * Symbol k of a stream lies in segment k / L, and segments are independent streams, so symbols
+ * [first, first + count) need segments j0 = first / L .. j1 = (first + count - 1) / L and nothing
+ * else.  Version 2's context phase and version 3's position, K0 phase and neighbour validity all
+ * follow from the absolute index k, so the formats above are unchanged. */
+
+/* The segment span (*j0, *nj = j1 - j0 + 1) of a symbol range and the byte extent [*byte_off,
+ * *byte_off + *byte_len), relative to the container's start, of those segments' payloads.  Works
+ * on a container of any of the three versions, following its version byte, and needs only the
+ * header and the u16 length table in buf[0..nbytes): payload bytes may be absent.  Outputs may be
+ * NULL.  TIC_EINVAL for a bad header (magic, version, reserved bytes, L, n), a length table that
+ * is not wholly present, count == 0 or a range that is not inside [0, n). */
+int tic_rcseg_range_extent(const uint8_t* buf, size_t nbytes, size_t first, size_t count, size_t* j0, size_t* nj,
+                           size_t* byte_off, size_t* byte_len);
+/* tic_rcseg_decode / _ctx / _nbr of a symbol range: the same arguments and the same validation
+ * (the whole container is parsed; n, K, K0, geometry, neighbours, CRC), then TIC_EINVAL for
+ * count == 0 or a range not inside [0, n).  Write exactly count symbols to sym_out, equal to
+ * sym[first .. first + count) of the full decode.  A segment is decoded from its start up to the
+ * range's end; no payload byte outside tic_rcseg_range_extent's extent is read.  The full
+ * decoders are these with the range [0, n).  They are the reference of the device entries
+ * tic_entropy_decode_ranges*_device. */
+int tic_rcseg_decode_range(const uint8_t* buf, size_t nbytes, const int64_t* cum_freq, size_t ncum, uint8_t* sym_out,
+                           size_t n, size_t first, size_t count);
+int tic_rcseg_decode_range_ctx(const uint8_t* buf, size_t nbytes, const int64_t* tables, size_t K, size_t ncum,
+                               uint8_t* sym_out, size_t n, size_t first, size_t count);
+int tic_rcseg_decode_range_nbr(const uint8_t* buf, size_t nbytes, const int64_t* tables, size_t K0,
+                               uint32_t neighbours, size_t ncum, uint32_t eh, uint32_t ew, uint32_t C,
+                               uint8_t* sym_out, size_t n, size_t first, size_t count);
+
 /* --- segmented streams on the device (csrc/tic_entropy.cpp) ---
  * One range coder per lane, one segment each; a scan over the segment lengths; a gather that
  * writes the containers.  All entries are asynchronous on the handle's stream, never synchronise,
@@ -515,6 +544,90 @@ int tic_entropy_decode_nbr_device(tic_handle* h, const uint8_t* d_blob, const in
  * np.histogram's bins as tic_histogram_device).  Accumulates; integer adds only. */
 int tic_histogram_nbr_device(tic_handle* h, const uint8_t* d_sym, const int64_t* sym_offsets, const int64_t* counts,
                              int n_streams, int Q, uint32_t L, uint64_t* d_counts);
+
+/* --- symbol ranges of segmented streams on the device ---
+ * tic_entropy_decode_device / _ctx_device / _nbr_device for one symbol range per record.  Range r:
+ * symbols [firsts[r], firsts[r] + counts[r]) of the container of blob_sizes[r] bytes at d_blob +
+ * blob_offsets[r], which holds stream_counts[r] symbols (the header's n), go to d_sym +
+ * sym_offsets[r] (any alignment, order and gaps); bytes of d_sym outside the ranges are not
+ * written.  Several ranges may name one container.  All six arrays are HOST arrays of n_ranges
+ * entries, read during the call only.  For a valid container the symbols equal those of
+ * tic_rcseg_decode_range / _ctx / _nbr.  A container whose header does not fit stream_counts[r],
+ * its size or what was set on the handle (version, K / K0, CRC, geometry, neighbours) yields
+ * zeros for its ranges, as does a range whose segments' payloads would end outside the container.
+ * The kernels read the header, the u16 lengths of segments 0 .. j1 and the payloads of segments
+ * j0 .. j1 of each range (j0 = first / L, j1 = (first + count - 1) / L), and nothing else of a
+ * container: the other bytes need not be on the device.  One segment per lane: a lane decodes its
+ * segment from the start, as the chain cannot begin in the middle, up to the range's end, and
+ * stores only the symbols inside the range.  Asynchronous on the handle's stream, no
+ * synchronisation, no atomics.  TIC_EINVAL with nothing launched for what the entries above
+ * reject, and for counts[r] <= 0, firsts[r] < 0 or a range not inside stream_counts[r];
+ * n_ranges == 0 does nothing. */
+
+/* Device scratch (bytes) the three entries need for these ranges at segment length L (the
+ * smallest L of the containers): room for the most segments a range of counts[r] symbols can
+ * touch, wherever it starts.  Host arithmetic only. */
+int tic_entropy_ranges_scratch_bytes(const int64_t* firsts, const int64_t* counts, int n_ranges, uint32_t L,
+                                     size_t* bytes);
+int tic_entropy_decode_ranges_device(tic_handle* h, const uint8_t* d_blob, const int64_t* blob_offsets,
+                                     const int64_t* blob_sizes, const int64_t* stream_counts, const int64_t* firsts,
+                                     const int64_t* counts, int n_ranges, uint8_t* d_sym, const int64_t* sym_offsets,
+                                     void* d_scratch, size_t scratch_bytes);
+int tic_entropy_decode_ranges_ctx_device(tic_handle* h, const uint8_t* d_blob, const int64_t* blob_offsets,
+                                         const int64_t* blob_sizes, const int64_t* stream_counts,
+                                         const int64_t* firsts, const int64_t* counts, int n_ranges, uint8_t* d_sym,
+                                         const int64_t* sym_offsets, void* d_scratch, size_t scratch_bytes);
+/* Version 3: where the class rings of 64 lanes do not fit 64 KiB of LDS, 32 lanes of a workgroup
+ * work, each with its ring in LDS (a lane cannot re-read symbols it did not store). */
+int tic_entropy_decode_ranges_nbr_device(tic_handle* h, const uint8_t* d_blob, const int64_t* blob_offsets,
+                                         const int64_t* blob_sizes, const int64_t* stream_counts,
+                                         const int64_t* firsts, const int64_t* counts, int n_ranges, uint8_t* d_sym,
+                                         const int64_t* sym_offsets, void* d_scratch, size_t scratch_bytes);
+
+/* --- a region of an image (csrc/tic_region.cpp) ---
+ * Patches are independent and, in a segmented stream, so are the symbols of different segments:
+ * the rectangle [y, y + h) x [x, x + w) of an H x W image can be decoded from the patches it
+ * needs.  The patches py0 <= py < py1, px0 <= px < px1 of the image's grid, row-major, are the
+ * patch batch of an image of the box's size (the box clipped to H x W), so the decoder,
+ * tic_patches_to_images_device and tic_round_u8_device serve them unchanged; for every grid row
+ * of the box the patches px0 .. px1 - 1 are one contiguous symbol range of the stream
+ * (tic_entropy_decode_ranges*_device). */
+
+/* The patch box of a region.  S = 0: no post-filter, the box is the patch rows and columns the
+ * region touches.  S > 0 (even; 128 for the rmbe net): the region is first widened, per axis, over
+ * every window band of the post-filter's second pass it intersects, then over every band of the
+ * first pass the result intersects, with o = S / 2:
+ *   rows     pass 2: [o + a*S, o + a*S + S), a < (H - o) / S;  pass 1: [a*S, a*S + S), a < H / S
+ *   columns  pass 2: [b*S, b*S + S), b < W / S;                pass 1: [o + b*S, ...), b < (W - o) / S
+ * then aligned to P and clipped to the patch grid.  That is a superset of what the region's pixels
+ * depend on: a pixel's pass-2 window lies in the box, every pixel of that window has its pass-1
+ * window in the box, and further windows inside the box touch no pixel of the region, because the
+ * windows of one pass are disjoint.  The box exceeds the region's own patch box by less than
+ * 2*S + P pixels per side.  Host arithmetic: no device, no handle.  TIC_EINVAL for a region that
+ * is empty or not inside H x W, P <= 0 or a bad S. */
+int tic_region_plan(int H, int W, int P, int y, int x, int h, int w, int S, int* py0, int* py1, int* px0, int* px1);
+
+/* tic_rmbe_images_device on parts of images.  Region i is a float32 HWC block of heights[i] x
+ * widths[i] at offsets[i] (floats) of the arena and holds rows y0s[i].. and columns x0s[i].. of an
+ * image of full_heights[i] x full_widths[i].  Filters, in place, every first-pass window of the
+ * FULL image's grid (positions and counts as tic_rmbe_image_device for the full size, not the
+ * region's) that lies wholly inside the region, then every such second-pass window; pixels in no
+ * such window stay untouched.  One gather, one run of the network and one write-back per pass for
+ * the whole list.  A region at origin (0, 0) with the full size gives tic_rmbe_image_device's
+ * result bit for bit; a region that is tic_region_plan's box gives the full image's result on the
+ * pixels the box was planned for.  HOST arrays of n entries, read during the call only.
+ * TIC_MODEL_RMBE handle; TIC_EINVAL for a region not inside its image or overlapping regions. */
+int tic_rmbe_regions_device(tic_handle* h, float* d_arena, const int64_t* offsets, const int32_t* heights,
+                            const int32_t* widths, const int32_t* y0s, const int32_t* x0s,
+                            const int32_t* full_heights, const int32_t* full_widths, int n);
+
+/* Crop i: rows [ys[i], ys[i] + hs[i]) x columns [xs[i], xs[i] + ws[i]) of the uint8 HWC box of
+ * heights[i] x widths[i] at byte offsets[i] of d_boxes, as a dense [hs[i], ws[i], 3] block at byte
+ * out_offsets[i] of d_out (one launch for the list; bytes of d_out in no block are not written).
+ * Any handle.  TIC_EINVAL for a crop not inside its box or overlapping outputs. */
+int tic_crop_regions_device(tic_handle* h, const uint8_t* d_boxes, const int64_t* offsets, const int32_t* heights,
+                            const int32_t* widths, const int32_t* ys, const int32_t* xs, const int32_t* hs,
+                            const int32_t* ws, const int64_t* out_offsets, int n, uint8_t* d_out);
 
 #ifdef __cplusplus
 }

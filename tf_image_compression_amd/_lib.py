@@ -138,6 +138,26 @@ SIGNATURES = [
                                                C.c_size_t]),
     ("tic_histogram_nbr_device", C.c_int, [vp, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int, C.c_int,
                                           C.c_uint32, vp]),
+    # symbol ranges of a container: host reference
+    ("tic_rcseg_range_extent", C.c_int, [u8p, C.c_size_t, C.c_size_t, C.c_size_t] + [C.POINTER(C.c_size_t)] * 4),
+    ("tic_rcseg_decode_range", C.c_int, [u8p, C.c_size_t, C.POINTER(C.c_int64), C.c_size_t, u8p, C.c_size_t,
+                                        C.c_size_t, C.c_size_t]),
+    ("tic_rcseg_decode_range_ctx", C.c_int, [u8p, C.c_size_t, C.POINTER(C.c_int64), C.c_size_t, C.c_size_t, u8p,
+                                            C.c_size_t, C.c_size_t, C.c_size_t]),
+    ("tic_rcseg_decode_range_nbr", C.c_int, [u8p, C.c_size_t, C.POINTER(C.c_int64), C.c_size_t, C.c_uint32, C.c_size_t,
+                                            C.c_uint32, C.c_uint32, C.c_uint32, u8p, C.c_size_t, C.c_size_t,
+                                            C.c_size_t]),
+    # ... and on the device
+    ("tic_entropy_ranges_scratch_bytes", C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int, C.c_uint32,
+                                                  C.POINTER(C.c_size_t)]),
+] + [(name, C.c_int, [vp, vp] + [C.POINTER(C.c_int64)] * 5 + [C.c_int, vp, C.POINTER(C.c_int64), vp, C.c_size_t])
+     for name in ("tic_entropy_decode_ranges_device", "tic_entropy_decode_ranges_ctx_device",
+                  "tic_entropy_decode_ranges_nbr_device")] + [
+    # a region of an image: its patch box, the post-filter on parts of images, the final crop
+    ("tic_region_plan", C.c_int, [C.c_int] * 8 + [i32p] * 4),
+    ("tic_rmbe_regions_device", C.c_int, [vp, vp, C.POINTER(C.c_int64)] + [C.POINTER(C.c_int32)] * 6 + [C.c_int]),
+    ("tic_crop_regions_device", C.c_int, [vp, vp, C.POINTER(C.c_int64)] + [C.POINTER(C.c_int32)] * 6
+                                         + [C.POINTER(C.c_int64), C.c_int, vp]),
     ("tic_device_info", C.c_int, [vp, C.c_char_p, C.c_int]),
 ]
 

@@ -64,6 +64,13 @@ class DeviceView:
         self.nbytes = buf.nbytes - offset
         self.ptr = C.c_void_p(buf.ptr.value + offset)
 
+    def upload(self, arr: np.ndarray) -> None:
+        """``arr`` to the bytes from this view's offset on; the rest of the buffer stays as it was."""
+        arr = np.ascontiguousarray(arr)
+        if arr.nbytes > self.nbytes:
+            raise ValueError("array larger than the rest of the device buffer")
+        check(lib().tic_memcpy_h2d(self.codec._h, self.ptr, arr.ctypes.data, arr.nbytes), "tic_memcpy_h2d")
+
 
 class Codec:
     """A model_N codec on one GPU.  ``params``: TF-named float32 arrays (weights.py)."""
@@ -321,6 +328,47 @@ class Codec:
         check(lib().tic_rmbe_images_device(self._h, d_images.ptr, ptr(off, C.c_int64), ptr(hs, C.c_int32),
                                            ptr(ws, C.c_int32), off.size), "tic_rmbe_images_device")
 
+    # a region of an image (tic_region.cpp)
+    @staticmethod
+    def region_plan(H: int, W: int, P: int, y: int, x: int, h: int, w: int, S: int = 0) -> tuple[int, int, int, int]:
+        """``(py0, py1, px0, px1)``: the patches ``py0 <= py < py1``, ``px0 <= px < px1`` the region
+        ``[y, y + h) x [x, x + w)`` of an ``H x W`` image needs; ``S``: the post-filter's window side
+        (128), 0 without it (tic_region_plan; host arithmetic)."""
+        vals = [int(v) for v in (H, W, P, y, x, h, w, S)]
+        if any(abs(v) >= 2 ** 31 for v in vals):
+            raise ValueError("region_plan: arguments must fit 32 bits")
+        out = [C.c_int() for _ in range(4)]
+        check(lib().tic_region_plan(*vals, *[C.byref(v) for v in out]), "tic_region_plan")
+        return tuple(v.value for v in out)
+
+    def rmbe_regions_device(self, d_arena: DeviceBuffer, offsets, sizes, origins, full_sizes):
+        """The post-filter on parts of images: region i, ``sizes[i]`` at float ``offsets[i]`` of the
+        arena, holds the pixels from ``origins[i] = (y0, x0)`` on of an image of ``full_sizes[i]``;
+        the windows of the full image's grid that lie wholly inside it are filtered in place
+        (tic_rmbe_regions_device)."""
+        off, hs, ws = self._image_table(offsets, sizes)
+        _, ys, xs = self._image_table(offsets, origins)
+        _, fh, fw = self._image_table(offsets, full_sizes)
+        i32 = C.c_int32
+        check(lib().tic_rmbe_regions_device(self._h, d_arena.ptr, ptr(off, C.c_int64), ptr(hs, i32), ptr(ws, i32),
+                                            ptr(ys, i32), ptr(xs, i32), ptr(fh, i32), ptr(fw, i32), off.size),
+              "tic_rmbe_regions_device")
+
+    def crop_regions_device(self, d_boxes: DeviceBuffer, offsets, sizes, origins, crop_sizes, out_offsets,
+                            d_out: DeviceBuffer):
+        """Crop i: ``crop_sizes[i]`` pixels from ``origins[i]`` on of the uint8 HWC box ``sizes[i]``
+        at byte ``offsets[i]`` -> a dense block at byte ``out_offsets[i]`` of ``d_out``
+        (tic_crop_regions_device)."""
+        off, hs, ws = self._image_table(offsets, sizes)
+        _, ys, xs = self._image_table(offsets, origins)
+        ooff, ch, cw = self._image_table(out_offsets, crop_sizes)
+        if ooff.size != off.size:
+            raise ValueError(f"{ooff.size} output offsets for {off.size} boxes")
+        i32 = C.c_int32
+        check(lib().tic_crop_regions_device(self._h, d_boxes.ptr, ptr(off, C.c_int64), ptr(hs, i32), ptr(ws, i32),
+                                            ptr(ys, i32), ptr(xs, i32), ptr(ch, i32), ptr(cw, i32),
+                                            ptr(ooff, C.c_int64), off.size, d_out.ptr), "tic_crop_regions_device")
+
     # MS-SSIM of lists of uint8 image pairs (tic_msssim.cpp)
     @staticmethod
     def msssim_scratch_bytes(sizes) -> int:
@@ -488,6 +536,38 @@ class Codec:
             raise ValueError(f"d_counts holds {d_counts.nbytes} bytes, [{rows}, {Q}] counts need {8 * rows * int(Q)}")
         check(lib().tic_histogram_nbr_device(self._h, d_sym.ptr, ptr(off, C.c_int64), ptr(cnt, C.c_int64), n, int(Q),
                                              int(segment), d_counts.ptr), "tic_histogram_nbr_device")
+
+    # symbol ranges of containers of any version (entropy.unpack_range is the host side)
+    @staticmethod
+    def entropy_ranges_scratch_bytes(firsts, counts, segment: int) -> int:
+        """Bytes of device scratch ``entropy_decode_ranges_device`` needs for these symbol ranges
+        (tic_entropy_ranges_scratch_bytes; ``segment`` is the smallest L of the containers)."""
+        n, (fst, cnt) = Codec._stream_table(firsts, counts)
+        out = C.c_size_t()
+        check(lib().tic_entropy_ranges_scratch_bytes(ptr(fst, C.c_int64), ptr(cnt, C.c_int64), n, int(segment),
+                                                     C.byref(out)), "tic_entropy_ranges_scratch_bytes")
+        return out.value
+
+    def entropy_decode_ranges_device(self, d_blob: DeviceBuffer, blob_offsets, blob_sizes, stream_counts, firsts,
+                                     counts, d_sym: DeviceBuffer, sym_offsets, d_scratch: DeviceBuffer,
+                                     scratch_bytes: int | None = None, version: int = 1) -> None:
+        """Range r: symbols ``[firsts[r], firsts[r] + counts[r])`` of the container at
+        ``blob_offsets[r]`` (``blob_sizes[r]`` bytes, ``stream_counts[r]`` symbols; several ranges
+        may name one container) -> ``counts[r]`` symbols at ``sym_offsets[r]`` of ``d_sym``.  Only
+        the header, the length table and the payloads of the range's segments are read, so the rest
+        of the container need not be on the device.  ``version`` 1, 2 or 3 selects
+        tic_entropy_decode_ranges_device, ``_ctx_device`` or ``_nbr_device`` (under the table or
+        tables set on this codec)."""
+        name = {1: "tic_entropy_decode_ranges_device", 2: "tic_entropy_decode_ranges_ctx_device",
+                3: "tic_entropy_decode_ranges_nbr_device"}.get(int(version))
+        if name is None:
+            raise ValueError(f"container version {version} is not 1, 2 or 3")
+        n, (boff, bsz, scnt, fst, cnt, soff) = self._stream_table(blob_offsets, blob_sizes, stream_counts, firsts,
+                                                                  counts, sym_offsets)
+        check(getattr(lib(), name)(
+            self._h, d_blob.ptr, ptr(boff, C.c_int64), ptr(bsz, C.c_int64), ptr(scnt, C.c_int64), ptr(fst, C.c_int64),
+            ptr(cnt, C.c_int64), n, d_sym.ptr, ptr(soff, C.c_int64), d_scratch.ptr,
+            d_scratch.nbytes if scratch_bytes is None else int(scratch_bytes)), name)
 
     def round_u8_device(self, d_in: DeviceBuffer, n: int, d_out: DeviceBuffer):
         check(lib().tic_round_u8_device(self._h, d_in.ptr, n, d_out.ptr), "tic_round_u8_device")

@@ -295,11 +295,12 @@ int check_nbr_tables(const int64_t* tables, const NbrModel& m, std::vector<int64
 }
 
 // The row of every symbol of one segment, in order: (c, w, h) and the K0 phase are counters that
-// wrap, as on the device.  sym: the stream's symbols, those before the current one valid.
+// wrap, as on the device.  sym: the segment's own symbols, those before the current one valid (a
+// neighbour in an earlier segment never counts, so nothing in front of the segment is read).
 struct NbrWalk {
   const NbrModel& m;
-  const uint8_t* sym;
-  size_t b;  // the segment's first symbol
+  const uint8_t* sym;  // the segment's symbols: sym[0] is symbol b of the stream
+  size_t b;            // the segment's first symbol
   size_t nsym, rowC;
   uint32_t c, w, h;
   size_t k0;
@@ -312,7 +313,7 @@ struct NbrWalk {
     h = (uint32_t)(p / rowC);
     k0 = b % m.K0;
   }
-  size_t t(size_t j) const { return 1 + (2 * (size_t)sym[j] >= nsym ? 1 : 0); }
+  size_t t(size_t j) const { return 1 + (2 * (size_t)sym[j - b] >= nsym ? 1 : 0); }
   size_t row(size_t i) const {  // of symbol i; then advance() before the next
     size_t nb = (w >= 1 && i - b >= m.C) ? t(i - m.C) : 0;
     if (m.neighbours == 2 && h >= 1 && i - b >= rowC) nb += 3 * t(i - rowC);
@@ -327,6 +328,58 @@ struct NbrWalk {
         if (++h == m.eh) h = 0;
       }
     }
+  }
+};
+
+// --- symbol ranges (tic_rcseg_decode_range*) ---
+int check_range(size_t n, size_t first, size_t count) {
+  if (count == 0) return rc_fail(TIC_EINVAL, "symbol range: no symbols");
+  if (first >= n || count > n - first)
+    return rc_fail(TIC_EINVAL, "symbol range [" + std::to_string(first) + ", " + std::to_string(first) + " + " + std::to_string(count) +
+                                   ") is not inside the stream's " + std::to_string(n) + " symbols");
+  return TIC_OK;
+}
+
+// The segments j0 .. j1 that hold symbols [first, first + count) of a parsed container, one after
+// another: [b, e) the segment's symbols, p / len its payload.  A segment is decoded from its
+// start (the chain cannot begin in the middle): begin() is where its symbols go, straight into
+// the output when the whole segment lies in the range, else a buffer of its own, from which
+// commit() copies the part inside the range.  Payloads in front of j0 are skipped by their
+// lengths, those behind j1 never looked at.
+struct RangeWalk {
+  const uint8_t *lens, *p;
+  size_t n, L, first, count, j, j1, b = 0, e = 0, len = 0;
+  uint8_t* out;
+  std::vector<uint8_t> tmp;
+  RangeWalk(const uint8_t* buf, size_t header, size_t n_, size_t L_, size_t first_, size_t count_, uint8_t* out_)
+      : lens(buf + header), n(n_), L(L_), first(first_), count(count_), out(out_) {
+    const size_t S = (n + L - 1) / L;
+    p = lens + 2 * S;
+    j1 = (first + count - 1) / L;
+    for (j = 0; j < first / L; ++j) p += seg_len(j);
+    load();
+  }
+  size_t seg_len(size_t k) const { return (size_t)lens[2 * k] | (size_t)lens[2 * k + 1] << 8; }
+  void load() {
+    if (j > j1) return;
+    len = seg_len(j);
+    b = j * L;
+    e = std::min(std::min(n, b + L), first + count);  // nothing behind the range is decoded
+  }
+  bool more() const { return j <= j1; }
+  void next() {
+    p += len;
+    ++j;
+    load();
+  }
+  bool direct() const { return b >= first; }
+  uint8_t* begin() {
+    if (direct()) return out + (b - first);
+    tmp.resize(e - b);
+    return tmp.data();
+  }
+  void commit() {
+    if (!direct()) memcpy(out, tmp.data() + (first - b), e - first);
   }
 };
 }  // namespace
@@ -483,7 +536,8 @@ int tic_rcseg_parse(const uint8_t* buf, size_t nbytes, uint32_t* L_out, uint64_t
   return parse_framing(buf, nbytes, kSegHeader, L_out, n_out);
 }
 
-int tic_rcseg_decode(const uint8_t* buf, size_t nbytes, const int64_t* cum, size_t ncum, uint8_t* sym_out, size_t n) {
+int tic_rcseg_decode_range(const uint8_t* buf, size_t nbytes, const int64_t* cum, size_t ncum, uint8_t* sym_out,
+                           size_t n, size_t first, size_t count) {
   if (!sym_out) return rc_fail(TIC_EINVAL, "null argument");
   uint32_t L = 0;
   uint64_t hn = 0;
@@ -493,20 +547,23 @@ int tic_rcseg_decode(const uint8_t* buf, size_t nbytes, const int64_t* cum, size
     return rc_fail(TIC_EINVAL, "segmented stream holds " + std::to_string(hn) + " symbols, " + std::to_string(n) + " expected");
   int64_t total = 0;
   if ((rc = check_seg_table(cum, ncum, &total))) return rc;
-  const size_t S = (n + L - 1) / L;
-  const uint8_t* lens = buf + kSegHeader;
-  const uint8_t* p = lens + 2 * S;
-  for (size_t j = 0; j < S; ++j) {
-    const size_t len = (size_t)lens[2 * j] | (size_t)lens[2 * j + 1] << 8;
-    const size_t b = j * L, e = std::min(n, b + L);
+  if ((rc = check_range(n, first, count))) return rc;
+  RangeWalk rw(buf, kSegHeader, n, L, first, count, sym_out);
+  for (; rw.more(); rw.next()) {
     DecCore<MemSource> c;
-    c.s.p = p;
-    c.s.end = p + len;
+    c.s.p = rw.p;
+    c.s.end = rw.p + rw.len;
     c.start();
-    for (size_t i = b; i < e; ++i) sym_out[i] = (uint8_t)c.symbol(cum, (int64_t)ncum - 1, (uint64_t)total);
-    p += len;
+    uint8_t* seg = rw.begin();
+    for (size_t i = 0; i < rw.e - rw.b; ++i) seg[i] = (uint8_t)c.symbol(cum, (int64_t)ncum - 1, (uint64_t)total);
+    rw.commit();
   }
   return TIC_OK;
+}
+
+int tic_rcseg_decode(const uint8_t* buf, size_t nbytes, const int64_t* cum, size_t ncum, uint8_t* sym_out, size_t n) {
+  // n == 0 never passes: no container holds no symbols, so the count check fails first
+  return tic_rcseg_decode_range(buf, nbytes, cum, ncum, sym_out, n, 0, n);
 }
 
 // --- segmented stream, version 2 ---
@@ -580,8 +637,8 @@ int tic_rcseg_parse_ctx(const uint8_t* buf, size_t nbytes, uint32_t* L_out, uint
   return TIC_OK;
 }
 
-int tic_rcseg_decode_ctx(const uint8_t* buf, size_t nbytes, const int64_t* tables, size_t K, size_t ncum,
-                         uint8_t* sym_out, size_t n) {
+int tic_rcseg_decode_range_ctx(const uint8_t* buf, size_t nbytes, const int64_t* tables, size_t K, size_t ncum,
+                               uint8_t* sym_out, size_t n, size_t first, size_t count) {
   if (!sym_out) return rc_fail(TIC_EINVAL, "null argument");
   uint32_t L = 0, hK = 0, hcrc = 0;
   uint64_t hn = 0;
@@ -595,24 +652,27 @@ int tic_rcseg_decode_ctx(const uint8_t* buf, size_t nbytes, const int64_t* table
     return rc_fail(TIC_EINVAL, "context stream was coded under " + std::to_string(hK) + " tables, " + std::to_string(K) + " given");
   if (hcrc != ctx_tables_crc(tables, K * ncum))
     return rc_fail(TIC_EINVAL, "context stream: the tables' CRC-32C differs from the header's (coded under other tables)");
-  const size_t S = (n + L - 1) / L;
-  const uint8_t* lens = buf + kCtxHeader;
-  const uint8_t* p = lens + 2 * S;
-  for (size_t j = 0; j < S; ++j) {
-    const size_t len = (size_t)lens[2 * j] | (size_t)lens[2 * j + 1] << 8;
-    const size_t b = j * L, e = std::min(n, b + L);
+  if ((rc = check_range(n, first, count))) return rc;
+  RangeWalk rw(buf, kCtxHeader, n, L, first, count, sym_out);
+  for (; rw.more(); rw.next()) {
     DecCore<MemSource> c;
-    c.s.p = p;
-    c.s.end = p + len;
+    c.s.p = rw.p;
+    c.s.end = rw.p + rw.len;
     c.start();
-    size_t k = b % K;
-    for (size_t i = b; i < e; ++i) {
-      sym_out[i] = (uint8_t)c.symbol(tables + k * ncum, (int64_t)ncum - 1, (uint64_t)totals[k]);
+    uint8_t* seg = rw.begin();
+    size_t k = rw.b % K;
+    for (size_t i = 0; i < rw.e - rw.b; ++i) {
+      seg[i] = (uint8_t)c.symbol(tables + k * ncum, (int64_t)ncum - 1, (uint64_t)totals[k]);
       if (++k == K) k = 0;
     }
-    p += len;
+    rw.commit();
   }
   return TIC_OK;
+}
+
+int tic_rcseg_decode_ctx(const uint8_t* buf, size_t nbytes, const int64_t* tables, size_t K, size_t ncum,
+                         uint8_t* sym_out, size_t n) {
+  return tic_rcseg_decode_range_ctx(buf, nbytes, tables, K, ncum, sym_out, n, 0, n);
 }
 
 // --- segmented stream, version 3 ---
@@ -656,7 +716,7 @@ int tic_rcseg_encode_nbr(const uint8_t* sym, size_t n, uint32_t L, const int64_t
     const size_t b = j * L, e = std::min(n, b + L);
     EncCore<MemSink> c;
     c.s.p = p;
-    NbrWalk walk(m, sym, b);
+    NbrWalk walk(m, sym + b, b);
     for (size_t i = b; i < e; ++i) {
       const size_t s = sym[i], k = walk.row(i);
       const int64_t* cum = tables + k * ncum;
@@ -699,8 +759,9 @@ int tic_rcseg_parse_nbr(const uint8_t* buf, size_t nbytes, uint32_t* L_out, uint
   return TIC_OK;
 }
 
-int tic_rcseg_decode_nbr(const uint8_t* buf, size_t nbytes, const int64_t* tables, size_t K0, uint32_t neighbours,
-                         size_t ncum, uint32_t eh, uint32_t ew, uint32_t C, uint8_t* sym_out, size_t n) {
+int tic_rcseg_decode_range_nbr(const uint8_t* buf, size_t nbytes, const int64_t* tables, size_t K0,
+                               uint32_t neighbours, size_t ncum, uint32_t eh, uint32_t ew, uint32_t C,
+                               uint8_t* sym_out, size_t n, size_t first, size_t count) {
   if (!sym_out) return rc_fail(TIC_EINVAL, "null argument");
   uint32_t L = 0, hK0 = 0, hcrc = 0, heh = 0, hew = 0, hC = 0, hnb = 0;
   uint64_t hn = 0;
@@ -722,24 +783,61 @@ int tic_rcseg_decode_nbr(const uint8_t* buf, size_t nbytes, const int64_t* table
     return rc_fail(TIC_EINVAL, "neighbour stream was coded with neighbours " + std::to_string(hnb) + ", " + std::to_string(neighbours) + " given");
   if (hcrc != ctx_tables_crc(tables, K0 * m.M * ncum))
     return rc_fail(TIC_EINVAL, "neighbour stream: the tables' CRC-32C differs from the header's (coded under other tables)");
-  const size_t S = (n + L - 1) / L;
-  const uint8_t* lens = buf + kNbrHeader;
-  const uint8_t* p = lens + 2 * S;
-  for (size_t j = 0; j < S; ++j) {
-    const size_t len = (size_t)lens[2 * j] | (size_t)lens[2 * j + 1] << 8;
-    const size_t b = j * L, e = std::min(n, b + L);
+  if ((rc = check_range(n, first, count))) return rc;
+  RangeWalk rw(buf, kNbrHeader, n, L, first, count, sym_out);
+  for (; rw.more(); rw.next()) {
     DecCore<MemSource> c;
-    c.s.p = p;
-    c.s.end = p + len;
+    c.s.p = rw.p;
+    c.s.end = rw.p + rw.len;
     c.start();
-    NbrWalk walk(m, sym_out, b);
-    for (size_t i = b; i < e; ++i) {
+    uint8_t* seg = rw.begin();
+    NbrWalk walk(m, seg, rw.b);
+    for (size_t i = rw.b; i < rw.e; ++i) {
       const size_t k = walk.row(i);
-      sym_out[i] = (uint8_t)c.symbol(tables + k * ncum, (int64_t)ncum - 1, (uint64_t)totals[k]);
+      seg[i - rw.b] = (uint8_t)c.symbol(tables + k * ncum, (int64_t)ncum - 1, (uint64_t)totals[k]);
       walk.advance();
     }
-    p += len;
+    rw.commit();
   }
+  return TIC_OK;
+}
+
+int tic_rcseg_decode_nbr(const uint8_t* buf, size_t nbytes, const int64_t* tables, size_t K0, uint32_t neighbours,
+                         size_t ncum, uint32_t eh, uint32_t ew, uint32_t C, uint8_t* sym_out, size_t n) {
+  return tic_rcseg_decode_range_nbr(buf, nbytes, tables, K0, neighbours, ncum, eh, ew, C, sym_out, n, 0, n);
+}
+
+// The segments and payload bytes a symbol range needs, from the header and the length table alone.
+int tic_rcseg_range_extent(const uint8_t* buf, size_t nbytes, size_t first, size_t count, size_t* j0_out, size_t* nj_out,
+                           size_t* byte_off, size_t* byte_len) {
+  if (!buf) return rc_fail(TIC_EINVAL, "null argument");
+  if (nbytes < kSegHeader) return rc_fail(TIC_EINVAL, "not a segmented stream: shorter than its 20-byte header");
+  if (memcmp(buf, kSegMagic, 4) != 0) return rc_fail(TIC_EINVAL, "not a segmented stream: magic is not \"TICS\"");
+  const size_t header = buf[4] == 1 ? kSegHeader : buf[4] == 2 ? kCtxHeader : buf[4] == 3 ? kNbrHeader : 0;
+  if (!header) return rc_fail(TIC_EINVAL, "segmented stream version " + std::to_string(buf[4]) + " is not supported");
+  if (buf[5] || buf[6] || buf[7]) return rc_fail(TIC_EINVAL, "segmented stream: reserved bytes are not zero");
+  if (nbytes < header)
+    return rc_fail(TIC_EINVAL, "segmented stream: shorter than its " + std::to_string(header) + "-byte header");
+  const uint32_t L = rd32(buf + 8);
+  const uint64_t n = rd64(buf + 12);
+  if (!seg_L_ok(L)) return rc_fail(TIC_EINVAL, "segmented stream: segment length " + std::to_string(L) + " must be a multiple of 4 in [4, 16384]");
+  if (n == 0) return rc_fail(TIC_EINVAL, "segmented stream: no symbols");
+  if (n > (UINT64_MAX >> 3) || (n + L - 1) / L > (nbytes - header) / 2)
+    return rc_fail(TIC_EINVAL, "segmented stream: truncated inside the length table");
+  const int rc = check_range((size_t)n, first, count);
+  if (rc) return rc;
+  const uint64_t S = (n + L - 1) / L, j0 = first / L, j1 = (first + count - 1) / L;
+  const uint8_t* lens = buf + header;
+  uint64_t off = header + 2 * S, len = 0;
+  for (uint64_t j = 0; j <= j1; ++j) {
+    const uint64_t l = (uint64_t)lens[2 * j] | (uint64_t)lens[2 * j + 1] << 8;
+    if (j < j0) off += l;
+    else len += l;
+  }
+  if (j0_out) *j0_out = (size_t)j0;
+  if (nj_out) *nj_out = (size_t)(j1 - j0 + 1);
+  if (byte_off) *byte_off = (size_t)off;
+  if (byte_len) *byte_len = (size_t)len;
   return TIC_OK;
 }
 

@@ -52,7 +52,13 @@
 // a third pair of coder kernels, ent_encode_nbr_kernel / ent_decode_nbr_kernel, with
 // ent_histogram_nbr_kernel for its tables; they follow the version-2 kernels below.
 //
-// This file closes the one translation unit of the host runtime (it includes tic_msssim.cpp).
+// Symbol ranges (tic_entropy_decode_ranges*_device): the decoder's kernels are templates over RNG.
+// RNG = 0 decodes whole containers, the code the entries above have always launched; RNG = 1 takes
+// one range [first, first + count) per record, the work items being the segments of all ranges
+// (struct EntRng below).  There is no second copy of the decode arithmetic for them.
+//
+// This file is part of the one translation unit of the host runtime: it includes tic_msssim.cpp,
+// and tic_region.cpp includes it.
 #define tic_destroy tic_destroy_runtime_
 #include "tic_msssim.cpp"
 #undef tic_destroy
@@ -82,6 +88,22 @@ struct EntRec {
   long long in_off, in_size, count, out_off;
   uint32_t L, valid;
 };
+
+// A symbol range [first, first + count) of a container (tic_entropy_decode_ranges*_device).  The
+// decoder's kernels are templates over RNG: 0 decodes whole containers and is the code the
+// entries without ranges have always launched (the trailing range arguments are never read);
+// 1 takes one range per record, its work items being the segments first / L ..
+// (first + count - 1) / L of the range's container.
+struct EntRng {
+  long long first, count;
+};
+// The ranges of one chunk of records, by value beside EntChunk; nothing for RNG = 0.
+template <int RNG>
+struct EntRngChunk {
+  long long first[kEntStreams], count[kEntStreams];
+};
+template <>
+struct EntRngChunk<0> {};
 
 __host__ __device__ __forceinline__ uint32_t ent_stride(uint32_t L) { return 3 * L + 4; }
 
@@ -330,11 +352,14 @@ __global__ void __launch_bounds__(256) ent_gather_kernel(const EntRec* __restric
 
 // Lane k: the header of container first + k against the caller's count and size and, version 2,
 // against the K and the CRC of the tables set and, version 3, the geometry words g0, g1 as well.
-template <int HDR>
+// RNG: record k is a range of its container; seg_cnt receives the segments the range touches, and a
+// range that is empty or not inside the header's n makes the record invalid.
+template <int HDR, int RNG>
 __global__ void __launch_bounds__(64) ent_dec_header_kernel(const EntChunk t, const uint8_t* __restrict__ blob,
                                                             uint32_t K, uint32_t crc, uint32_t g0, uint32_t g1,
                                                             EntRec* __restrict__ rec,
-                                                            unsigned long long* __restrict__ seg_cnt) {
+                                                            unsigned long long* __restrict__ seg_cnt,
+                                                            const EntRngChunk<RNG> rg, EntRng* __restrict__ rng) {
   const int k = threadIdx.x;
   if (k >= t.n) return;
   EntRec r;
@@ -374,6 +399,11 @@ __global__ void __launch_bounds__(64) ent_dec_header_kernel(const EntChunk t, co
       S = (n + L - 1) / L;
       if (S > (unsigned long long)(r.in_size - HDR) / 2) ok = false;
     }
+    if constexpr (RNG != 0) {
+      const unsigned long long a = (unsigned long long)rg.first[k], c = (unsigned long long)rg.count[k];
+      if (ok && (c == 0 || a >= n || c > n - a)) ok = false;
+      if (ok) S = (a + c - 1) / L - a / L + 1;
+    }
     if (ok) {
       r.L = L;
       r.valid = 1;
@@ -383,46 +413,71 @@ __global__ void __launch_bounds__(64) ent_dec_header_kernel(const EntChunk t, co
   }
   rec[t.first + k] = r;
   seg_cnt[t.first + k] = S;
+  if constexpr (RNG != 0) {
+    EntRng q;
+    q.first = rg.first[k];
+    q.count = rg.count[k];
+    rng[t.first + k] = q;
+  }
 }
 
 // Workgroup i: the offsets of container i's payloads from its u16 lengths; a container that
 // cannot be decoded (header, or its segments do not fit the scratch) becomes zeros.
-template <int HDR>
+// RNG: record i is a range; the scan still runs over segments 0 .. j1 of its container, to find
+// the payload offsets, but keeps only those of j0 .. j1 (work item b + j - j0) and reads no length
+// behind j1.  A range whose last payload would end outside the container becomes zeros too; only
+// the range's own bytes of d_sym are ever written.
+template <int HDR, int RNG>
 __global__ void __launch_bounds__(256) ent_dec_scan_kernel(const uint8_t* __restrict__ blob, EntRec* __restrict__ rec,
                                                            const unsigned long long* __restrict__ seg_base,
                                                            unsigned long long cap,
                                                            unsigned long long* __restrict__ seg_off,
-                                                           uint8_t* __restrict__ d_sym) {
+                                                           uint8_t* __restrict__ d_sym,
+                                                           const EntRng* __restrict__ rng) {
   __shared__ unsigned long long s[256];
   const int i = blockIdx.x, t = threadIdx.x;
   const EntRec r = rec[i];
   const unsigned long long b = seg_base[i], S = seg_base[i + 1] - b;
+  const long long fill = RNG ? rng[i].count : r.count;
   if (!r.valid || b + S > cap) {
     uint8_t* dst = d_sym + r.out_off;
-    for (long long k = t; k < r.count; k += 256) dst[k] = 0;
+    for (long long k = t; k < fill; k += 256) dst[k] = 0;
     if (t == 0) rec[i].valid = 0;
     return;
   }
   const uint8_t* lens = blob + r.in_off + HDR;
-  unsigned long long carry = (unsigned long long)HDR + 2ull * S;
-  for (unsigned long long j0 = 0; j0 < S; j0 += 256) {
-    const unsigned long long j = j0 + t;
-    const uint32_t len = j < S ? (uint32_t)lens[2 * j] | (uint32_t)lens[2 * j + 1] << 8 : 0;
+  // segments of the container; the first the record needs; one past the last it needs
+  const unsigned long long Sc = RNG ? ((unsigned long long)r.count + r.L - 1) / r.L : S;
+  const unsigned long long j0 = RNG ? (unsigned long long)rng[i].first / r.L : 0, je = j0 + S;
+  unsigned long long carry = (unsigned long long)HDR + 2ull * Sc;
+  for (unsigned long long jb = 0; jb < je; jb += 256) {
+    const unsigned long long j = jb + t;
+    const uint32_t len = j < je ? (uint32_t)lens[2 * j] | (uint32_t)lens[2 * j + 1] << 8 : 0;
     const unsigned long long inc = ent_block_scan(len, s);
-    if (j < S) seg_off[b + j] = carry + inc - len;
+    if (j < je && j >= j0) seg_off[b + j - j0] = carry + inc - len;
     carry += s[255];
     __syncthreads();
+  }
+  if (RNG && carry > (unsigned long long)r.in_size) {  // uniform: every thread holds the same carry
+    uint8_t* dst = d_sym + r.out_off;
+    for (long long k = t; k < fill; k += 256) dst[k] = 0;
+    if (t == 0) rec[i].valid = 0;
   }
 }
 
 // One segment per lane, grid-stride.  Dynamic LDS: the cumulative table, then (lut != 0) the
 // value -> symbol bytes.  The decode step has a second copy in ent_decode_ctx_kernel: a fix to the
 // arithmetic goes into both.
+// RNG (here and in the two decode kernels below): work item g of record i is segment j0 + (g -
+// seg_base[i]) of the container.  The lane decodes it from its start, because the chain cannot
+// begin in the middle, stops at the range's end and stores only symbols first <= k < first + count.
+template <int RNG>
 __global__ void __launch_bounds__(64) ent_decode_kernel(const EntModel m, int lut, const uint8_t* __restrict__ blob,
                                                         const EntRec* __restrict__ rec,
                                                         const unsigned long long* __restrict__ seg_base, int n_streams,
                                                         const unsigned long long* __restrict__ seg_off,
-                                                        uint8_t* __restrict__ d_sym) {
+                                                        uint8_t* __restrict__ d_sym,
+                                                        const EntRng* __restrict__ rng) {
   extern __shared__ uint32_t s_dyn[];
   uint32_t* s_cum = s_dyn;
   uint8_t* s_lut = reinterpret_cast<uint8_t*>(s_dyn + 260);
@@ -452,9 +507,10 @@ __global__ void __launch_bounds__(64) ent_decode_kernel(const EntModel m, int lu
     const int i = ent_find(seg_base, n_streams, g);
     const EntRec r = rec[i];
     if (!r.valid) continue;
-    const unsigned long long j = g - seg_base[i];
+    unsigned long long j = g - seg_base[i];
+    if constexpr (RNG != 0) j += (unsigned long long)rng[i].first / r.L;
     const long long left = r.count - (long long)(j * r.L);
-    const uint32_t cnt = left < (long long)r.L ? (uint32_t)left : r.L;
+    uint32_t cnt = left < (long long)r.L ? (uint32_t)left : r.L;
     const uint8_t* cont = blob + r.in_off;
     const uint32_t len = (uint32_t)cont[20 + 2 * j] | (uint32_t)cont[20 + 2 * j + 1] << 8;
     // the segment's extent, clamped to the container
@@ -464,6 +520,13 @@ __global__ void __launch_bounds__(64) ent_decode_kernel(const EntModel m, int lu
     unsigned long long end = pos + len;
     if (end > size) end = size;
     uint8_t* dst = d_sym + r.out_off + (long long)(j * r.L);
+    uint32_t lo = 0;  // the first symbol of the segment that is stored
+    if constexpr (RNG != 0) {
+      const long long first = rng[i].first, b = (long long)(j * r.L), stop = first + rng[i].count - b;
+      if (stop < (long long)cnt) cnt = (uint32_t)stop;
+      if (first > b) lo = (uint32_t)(first - b);
+      dst = d_sym + (r.out_off + b - first);  // dst[k] is touched for k >= lo only
+    }
 
     auto get = [&]() -> uint32_t { return pos < end ? (uint32_t)cont[pos++] : 0u; };
     uint32_t code = 0;
@@ -489,6 +552,7 @@ __global__ void __launch_bounds__(64) ent_decode_kernel(const EntModel m, int lu
     };
 
     uint32_t k = 0;
+    for (; k < lo; ++k) (void)dec();  // RNG: in front of the range
     for (; k < cnt && ((uintptr_t)(dst + k) & 3) != 0; ++k) dst[k] = (uint8_t)dec();
     for (; k + 4 <= cnt; k += 4) {
       uint32_t w = 0;
@@ -630,14 +694,15 @@ __global__ void __launch_bounds__(64) ent_encode_ctx_kernel(const uint32_t* __re
 
 // One segment per lane, grid-stride.  No value -> symbol bytes: with two symbols (ncum == 3, the
 // shipped models) the symbol is one compare with cum[1], otherwise the host's binary search.
-template <int LDS>
+template <int LDS, int RNG>
 __global__ void __launch_bounds__(64) ent_decode_ctx_kernel(const uint32_t* __restrict__ g_tab, uint32_t K,
                                                             uint32_t ncum, const uint8_t* __restrict__ blob,
                                                             const EntRec* __restrict__ rec,
                                                             const unsigned long long* __restrict__ seg_base,
                                                             int n_streams,
                                                             const unsigned long long* __restrict__ seg_off,
-                                                            uint8_t* __restrict__ d_sym) {
+                                                            uint8_t* __restrict__ d_sym,
+                                                            const EntRng* __restrict__ rng) {
   extern __shared__ uint32_t s_dyn[];
   const unsigned long long T = seg_base[n_streams];
   if ((unsigned long long)blockIdx.x * 64 >= T) return;
@@ -655,9 +720,10 @@ __global__ void __launch_bounds__(64) ent_decode_ctx_kernel(const uint32_t* __re
     const int i = ent_find(seg_base, n_streams, g);
     const EntRec r = rec[i];
     if (!r.valid) continue;
-    const unsigned long long j = g - seg_base[i];
+    unsigned long long j = g - seg_base[i];
+    if constexpr (RNG != 0) j += (unsigned long long)rng[i].first / r.L;
     const long long left = r.count - (long long)(j * r.L);
-    const uint32_t cnt = left < (long long)r.L ? (uint32_t)left : r.L;
+    uint32_t cnt = left < (long long)r.L ? (uint32_t)left : r.L;
     const uint8_t* cont = blob + r.in_off;
     const uint32_t len = (uint32_t)cont[28 + 2 * j] | (uint32_t)cont[28 + 2 * j + 1] << 8;
     // the segment's extent, clamped to the container
@@ -667,6 +733,13 @@ __global__ void __launch_bounds__(64) ent_decode_ctx_kernel(const uint32_t* __re
     unsigned long long end = pos + len;
     if (end > size) end = size;
     uint8_t* dst = d_sym + r.out_off + (long long)(j * r.L);
+    uint32_t lo = 0;  // the first symbol of the segment that is stored
+    if constexpr (RNG != 0) {
+      const long long first = rng[i].first, b = (long long)(j * r.L), stop = first + rng[i].count - b;
+      if (stop < (long long)cnt) cnt = (uint32_t)stop;
+      if (first > b) lo = (uint32_t)(first - b);
+      dst = d_sym + (r.out_off + b - first);  // dst[k] is touched for k >= lo only
+    }
     uint32_t row = (uint32_t)((j * r.L) % K) * ncum;
 
     auto get = [&]() -> uint32_t { return pos < end ? (uint32_t)cont[pos++] : 0u; };
@@ -713,6 +786,7 @@ __global__ void __launch_bounds__(64) ent_decode_ctx_kernel(const uint32_t* __re
     };
 
     uint32_t k = 0;
+    for (; k < lo; ++k) (void)dec();  // RNG: in front of the range
     for (; k < cnt && ((uintptr_t)(dst + k) & 3) != 0; ++k) dst[k] = (uint8_t)dec();
     for (; k + 4 <= cnt; k += 4) {
       uint32_t w = 0;
@@ -938,37 +1012,44 @@ __global__ void __launch_bounds__(64) ent_encode_nbr_kernel(const uint32_t* __re
 
 // One segment per lane, grid-stride.  Dynamic LDS: the tables (LDS), then the rings (RING).
 // d_sym is not __restrict__: with !RING a lane loads bytes it stored.
-template <int LDS, int RING>
+// RNG: a lane does not store the symbols in front of its range, so it cannot re-read them: where
+// the rings of 64 lanes exceed 64 KiB (!RING), 32 lanes of the workgroup work (LN), each with its
+// ring in LDS (at most 16383 bits, 2 KiB), and the other 32 only help to stage the tables.
+template <int LDS, int RING, int RNG>
 __global__ void __launch_bounds__(64) ent_decode_nbr_kernel(const uint32_t* __restrict__ g_tab, const EntNbr q,
                                                             const uint8_t* __restrict__ blob,
                                                             const EntRec* __restrict__ rec,
                                                             const unsigned long long* __restrict__ seg_base,
                                                             int n_streams,
                                                             const unsigned long long* __restrict__ seg_off,
-                                                            uint8_t* d_sym) {
+                                                            uint8_t* d_sym, const EntRng* __restrict__ rng) {
+  constexpr int LN = (RNG != 0 && !RING) ? 32 : 64;  // working lanes; ring words of a lane lie LN apart
+  constexpr bool kRing = RING || RNG != 0;
   extern __shared__ uint32_t s_dyn[];
   const unsigned long long T = seg_base[n_streams];
-  if ((unsigned long long)blockIdx.x * 64 >= T) return;
+  if ((unsigned long long)blockIdx.x * LN >= T) return;
   const uint32_t ncum = q.ncum, words = q.K0 * q.M * ncum;
   if (LDS) {
     for (uint32_t k = threadIdx.x; k < words; k += 64) s_dyn[k] = g_tab[k];
     __syncthreads();
   }
   auto tab = [&](uint32_t k) -> uint32_t { return LDS ? s_dyn[k] : g_tab[k]; };
-  uint32_t* ring = s_dyn + (LDS ? words : 0) + threadIdx.x;  // this lane's words, 64 apart
+  if (LN < 64 && threadIdx.x >= LN) return;  // behind the barrier above
+  uint32_t* ring = s_dyn + (LDS ? words : 0) + threadIdx.x;  // this lane's words, LN apart
   const uint32_t R = q.ring;
   const bool useN = q.two && q.rowC == R;  // else no segment reaches its N neighbour
   const uint32_t nsym = ncum - 1;
   const bool two = ncum == 3;
 
-  for (unsigned long long g = (unsigned long long)blockIdx.x * 64 + threadIdx.x; g < T;
-       g += (unsigned long long)gridDim.x * 64) {
+  for (unsigned long long g = (unsigned long long)blockIdx.x * LN + threadIdx.x; g < T;
+       g += (unsigned long long)gridDim.x * LN) {
     const int i = ent_find(seg_base, n_streams, g);
     const EntRec r = rec[i];
     if (!r.valid) continue;
-    const unsigned long long j = g - seg_base[i];
+    unsigned long long j = g - seg_base[i];
+    if constexpr (RNG != 0) j += (unsigned long long)rng[i].first / r.L;
     const long long left = r.count - (long long)(j * r.L);
-    const uint32_t cnt = left < (long long)r.L ? (uint32_t)left : r.L;
+    uint32_t cnt = left < (long long)r.L ? (uint32_t)left : r.L;
     const uint8_t* cont = blob + r.in_off;
     const uint32_t len = (uint32_t)cont[36 + 2 * j] | (uint32_t)cont[36 + 2 * j + 1] << 8;
     // the segment's extent, clamped to the container
@@ -978,11 +1059,18 @@ __global__ void __launch_bounds__(64) ent_decode_nbr_kernel(const uint32_t* __re
     unsigned long long end = pos + len;
     if (end > size) end = size;
     uint8_t* dst = d_sym + r.out_off + (long long)(j * r.L);
+    uint32_t lo = 0;  // the first symbol of the segment that is stored
+    if constexpr (RNG != 0) {
+      const long long first = rng[i].first, b = (long long)(j * r.L), stop = first + rng[i].count - b;
+      if (stop < (long long)cnt) cnt = (uint32_t)stop;
+      if (first > b) lo = (uint32_t)(first - b);
+      dst = d_sym + (r.out_off + b - first);  // dst[k] is touched for k >= lo only
+    }
     EntNbrPos at;
     at.start(q, j * r.L);
     uint32_t rp = 0, rw = R ? (R - q.C % R) % R : 0;  // ring places of symbol k - R and of symbol k - C
     // the ring word that holds place rp, kept in a register and written back when rp leaves it
-    uint32_t far = RING && R ? ring[0] : 0u;
+    uint32_t far = kRing && R ? ring[0] : 0u;
 
     auto get = [&]() -> uint32_t { return pos < end ? (uint32_t)cont[pos++] : 0u; };
     uint32_t code = 0;
@@ -991,10 +1079,10 @@ __global__ void __launch_bounds__(64) ent_decode_nbr_kernel(const uint32_t* __re
     // symbol at segment-local index k
     auto dec = [&](uint32_t k) -> uint32_t {
       uint32_t nb = 0;
-      if (RING) {
+      if (kRing) {
         if (R) {
           // a place in the word under rp is read from the register: the word in LDS is older
-          const uint32_t near = (rw >> 5) == (rp >> 5) ? far : ring[(rw >> 5) * 64];
+          const uint32_t near = (rw >> 5) == (rp >> 5) ? far : ring[(rw >> 5) * LN];
           if (at.w && k >= q.C) nb = 1u + ((near >> (rw & 31)) & 1u);
           if (useN && at.h && k >= R) nb += 3u * (1u + ((far >> (rp & 31)) & 1u));
         }
@@ -1036,21 +1124,22 @@ __global__ void __launch_bounds__(64) ent_decode_nbr_kernel(const uint32_t* __re
         range <<= 8;
         code = (code << 8) | get();
       }
-      if (RING && R) {  // this symbol's class replaces that of symbol k - R
+      if (kRing && R) {  // this symbol's class replaces that of symbol k - R
         const uint32_t bit = 1u << (rp & 31), word = rp >> 5;
         far = 2u * s >= nsym ? far | bit : far & ~bit;
         if (++rp == R) rp = 0;
         if (++rw == R) rw = 0;
         if ((rp >> 5) != word) {
-          ring[word * 64] = far;
-          far = ring[(rp >> 5) * 64];
+          ring[word * LN] = far;
+          far = ring[(rp >> 5) * LN];
         }
       }
       return s;
     };
 
-    if (RING) {
+    if (kRing) {
       uint32_t k = 0;
+      for (; k < lo; ++k) (void)dec(k);  // RNG: in front of the range
       for (; k < cnt && ((uintptr_t)(dst + k) & 3) != 0; ++k) dst[k] = (uint8_t)dec(k);
       for (; k + 4 <= cnt; k += 4) {
         uint32_t w = 0;
@@ -1220,6 +1309,14 @@ int ent_encode(tic_handle* h, const uint8_t* d_sym, const int64_t* sym_offsets, 
 int ent_decode(tic_handle* h, const uint8_t* d_blob, const int64_t* blob_offsets, const int64_t* blob_sizes,
                const int64_t* counts, int n_streams, uint8_t* d_sym, const int64_t* sym_offsets, void* d_scratch,
                size_t scratch_bytes, int ver);
+// The same for one symbol range [firsts[r], firsts[r] + rcounts[r]) per record; counts: the
+// containers' n.
+int ent_decode_ranges(tic_handle* h, const uint8_t* d_blob, const int64_t* blob_offsets, const int64_t* blob_sizes,
+                      const int64_t* counts, const int64_t* firsts, const int64_t* rcounts, int n_ranges,
+                      uint8_t* d_sym, const int64_t* sym_offsets, void* d_scratch, size_t scratch_bytes, int ver);
+// Most segments a range of `count` symbols touches at segment length L, wherever it starts; no
+// larger at any longer L.
+long long ent_range_segments(long long count, uint32_t L) { return (count + L - 2) / L + 1; }
 int ent_upload_tables(tic_handle* h, const int64_t* tables, size_t K, size_t ncum, EntTables meta);
 
 }  // namespace
@@ -1424,6 +1521,48 @@ int tic_entropy_decode_nbr_device(tic_handle* h, const uint8_t* d_blob, const in
                     scratch_bytes, 3);
 }
 
+int tic_entropy_ranges_scratch_bytes(const int64_t* firsts, const int64_t* counts, int n_ranges, uint32_t L,
+                                     size_t* bytes) {
+  if (!bytes) return fail(TIC_EINVAL, "null bytes");
+  *bytes = 0;
+  if (n_ranges < 0) return fail(TIC_EINVAL, "n_ranges %d is negative", n_ranges);
+  if (n_ranges > 0 && (!firsts || !counts)) return fail(TIC_EINVAL, "null per-range array");
+  if (!ent_L_ok(L)) return fail(TIC_EINVAL, "segment length %u must be a multiple of 4 in [4, 16384]", L);
+  long long T = 0;
+  for (int i = 0; i < n_ranges; ++i) {
+    if (firsts[i] < 0 || counts[i] <= 0 || counts[i] > (1ll << 40))
+      return fail(TIC_EINVAL, "range %d: first %lld, count %lld", i, (long long)firsts[i], (long long)counts[i]);
+    T += ent_range_segments(counts[i], L);
+    if (T > INT_MAX) return fail(TIC_EINVAL, "more than 2^31 - 1 segments");
+  }
+  *bytes = ent_fixed(n_ranges) + (size_t)n_ranges * sizeof(tic::EntRng) + (size_t)T * 8;
+  return TIC_OK;
+}
+
+int tic_entropy_decode_ranges_device(tic_handle* h, const uint8_t* d_blob, const int64_t* blob_offsets,
+                                     const int64_t* blob_sizes, const int64_t* stream_counts, const int64_t* firsts,
+                                     const int64_t* counts, int n_ranges, uint8_t* d_sym, const int64_t* sym_offsets,
+                                     void* d_scratch, size_t scratch_bytes) {
+  return ent_decode_ranges(h, d_blob, blob_offsets, blob_sizes, stream_counts, firsts, counts, n_ranges, d_sym,
+                           sym_offsets, d_scratch, scratch_bytes, 1);
+}
+
+int tic_entropy_decode_ranges_ctx_device(tic_handle* h, const uint8_t* d_blob, const int64_t* blob_offsets,
+                                         const int64_t* blob_sizes, const int64_t* stream_counts,
+                                         const int64_t* firsts, const int64_t* counts, int n_ranges, uint8_t* d_sym,
+                                         const int64_t* sym_offsets, void* d_scratch, size_t scratch_bytes) {
+  return ent_decode_ranges(h, d_blob, blob_offsets, blob_sizes, stream_counts, firsts, counts, n_ranges, d_sym,
+                           sym_offsets, d_scratch, scratch_bytes, 2);
+}
+
+int tic_entropy_decode_ranges_nbr_device(tic_handle* h, const uint8_t* d_blob, const int64_t* blob_offsets,
+                                         const int64_t* blob_sizes, const int64_t* stream_counts,
+                                         const int64_t* firsts, const int64_t* counts, int n_ranges, uint8_t* d_sym,
+                                         const int64_t* sym_offsets, void* d_scratch, size_t scratch_bytes) {
+  return ent_decode_ranges(h, d_blob, blob_offsets, blob_sizes, stream_counts, firsts, counts, n_ranges, d_sym,
+                           sym_offsets, d_scratch, scratch_bytes, 3);
+}
+
 int tic_histogram_nbr_device(tic_handle* h, const uint8_t* d_sym, const int64_t* sym_offsets, const int64_t* counts,
                              int n_streams, int Q, uint32_t L, uint64_t* d_counts) {
   if (!h) return fail(TIC_EINVAL, "null handle");
@@ -1578,18 +1717,28 @@ int ent_encode(tic_handle* h, const uint8_t* d_sym, const int64_t* sym_offsets, 
   return check_launch();
 }
 
-int ent_decode(tic_handle* h, const uint8_t* d_blob, const int64_t* blob_offsets, const int64_t* blob_sizes,
-               const int64_t* counts, int n_streams, uint8_t* d_sym, const int64_t* sym_offsets, void* d_scratch,
-               size_t scratch_bytes, int ver) {
+// RNG = 0: whole containers (firsts, rcounts unused); 1: one symbol range per record.
+template <int RNG>
+int ent_decode_t(tic_handle* h, const uint8_t* d_blob, const int64_t* blob_offsets, const int64_t* blob_sizes,
+                 const int64_t* counts, const int64_t* firsts, const int64_t* rcounts, int n_streams, uint8_t* d_sym,
+                 const int64_t* sym_offsets, void* d_scratch, size_t scratch_bytes, int ver) {
   const bool ctx = ver >= 2, nbr = ver == 3;
   if (!h) return fail(TIC_EINVAL, "null handle");
   if (n_streams < 0) return fail(TIC_EINVAL, "n_streams %d is negative", n_streams);
   if (n_streams == 0) return TIC_OK;
   if (!d_blob || !d_scratch || !d_sym) return fail(TIC_EINVAL, "null device pointer");
   if (!blob_offsets || !blob_sizes || !counts || !sym_offsets) return fail(TIC_EINVAL, "null per-stream array");
+  if (RNG && (!firsts || !rcounts)) return fail(TIC_EINVAL, "null per-range array");
   const char* why = "";
-  const long long Tmin = ent_segments(counts, n_streams, tic::kEntMaxL, &why);
+  long long Tmin = ent_segments(counts, n_streams, tic::kEntMaxL, &why);
   if (Tmin < 0) return fail(TIC_EINVAL, "%s", why);
+  if (RNG) {
+    Tmin = n_streams;  // a range touches at least one segment
+    for (int i = 0; i < n_streams; ++i)
+      if (firsts[i] < 0 || rcounts[i] <= 0 || firsts[i] >= counts[i] || rcounts[i] > counts[i] - firsts[i])
+        return fail(TIC_EINVAL, "range %d: [%lld, %lld + %lld) is empty or not inside the stream's %lld symbols", i,
+                    (long long)firsts[i], (long long)firsts[i], (long long)rcounts[i], (long long)counts[i]);
+  }
   for (int i = 0; i < n_streams; ++i)
     if (blob_offsets[i] < 0 || blob_sizes[i] < 0 || sym_offsets[i] < 0)
       return fail(TIC_EINVAL, "stream %d: negative offset or size", i);
@@ -1598,9 +1747,11 @@ int ent_decode(tic_handle* h, const uint8_t* d_blob, const int64_t* blob_offsets
   int rc = ctx ? ent_tables(h, &tb, nbr) : ent_model(h, &m);
   if (rc) return rc;
   if (((uintptr_t)d_scratch & 15) != 0) return fail(TIC_EINVAL, "d_scratch must be 16-byte aligned");
-  const size_t fixed = ent_fixed(n_streams);
+  // RNG: the ranges lie between the records and the per-segment offsets
+  const size_t fixed = ent_fixed(n_streams) + (RNG ? (size_t)n_streams * sizeof(tic::EntRng) : 0);
   if (scratch_bytes < fixed + (size_t)Tmin * 8)
-    return fail(TIC_EINVAL, "scratch of %zu bytes is too small (tic_entropy_scratch_bytes)", scratch_bytes);
+    return fail(TIC_EINVAL, "scratch of %zu bytes is too small (tic_entropy_%sscratch_bytes)", scratch_bytes,
+                RNG ? "ranges_" : "");
   // segments the scratch has room for: the containers' own L decides how many there are
   const unsigned long long cap = std::min<unsigned long long>((scratch_bytes - fixed) / 8, INT_MAX);
 
@@ -1611,21 +1762,26 @@ int ent_decode(tic_handle* h, const uint8_t* d_blob, const int64_t* blob_offsets
   const tic::EntNbr q = nbr ? ent_nbr(tb) : tic::EntNbr{};
   const uint32_t g0 = nbr ? tb.eh | tb.ew << 16 : 0, g1 = nbr ? tb.C | tb.neighbours << 16 : 0;
   // version 3: a lane's ring of class bits, whole words, for each of a workgroup's 64 lanes
-  const size_t ring_bytes = nbr ? ((size_t)q.ring + 31) / 32 * 4 * 64 : 0;
+  size_t ring_bytes = nbr ? ((size_t)q.ring + 31) / 32 * 4 * 64 : 0;
   const bool ring = ring_bytes <= kEntLdsRings;
-  const size_t lds = ctx ? (in_lds ? tab_bytes : 0) + (ring ? ring_bytes : 0)
+  // RNG && !ring: 32 working lanes a workgroup, their rings in LDS all the same
+  const unsigned lanes = RNG && !ring ? 32 : 64;
+  if (RNG && !ring) ring_bytes /= 2;
+  const size_t lds = ctx ? (in_lds ? tab_bytes : 0) + (ring || RNG ? ring_bytes : 0)
                          : 260 * sizeof(uint32_t) + (lut ? ((size_t)total + 3) / 4 * 4 : 0);
-  const void* dec_nbr = in_lds ? (ring ? reinterpret_cast<const void*>(tic::ent_decode_nbr_kernel<1, 1>)
-                                       : reinterpret_cast<const void*>(tic::ent_decode_nbr_kernel<1, 0>))
-                               : (ring ? reinterpret_cast<const void*>(tic::ent_decode_nbr_kernel<0, 1>)
-                                       : reinterpret_cast<const void*>(tic::ent_decode_nbr_kernel<0, 0>));
+  const void* dec_nbr = in_lds ? (ring ? reinterpret_cast<const void*>(tic::ent_decode_nbr_kernel<1, 1, RNG>)
+                                       : reinterpret_cast<const void*>(tic::ent_decode_nbr_kernel<1, 0, RNG>))
+                               : (ring ? reinterpret_cast<const void*>(tic::ent_decode_nbr_kernel<0, 1, RNG>)
+                                       : reinterpret_cast<const void*>(tic::ent_decode_nbr_kernel<0, 0, RNG>));
   HIP_TRY(hipSetDevice(h->device));
   if (lds > 48 * 1024)
     HIP_TRY(hipFuncSetAttribute(nbr   ? dec_nbr
-                                : ctx ? reinterpret_cast<const void*>(tic::ent_decode_ctx_kernel<1>)
-                                      : reinterpret_cast<const void*>(tic::ent_decode_kernel),
+                                : ctx ? reinterpret_cast<const void*>(tic::ent_decode_ctx_kernel<1, RNG>)
+                                      : reinterpret_cast<const void*>(tic::ent_decode_kernel<RNG>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const EntScratch s = ent_carve(d_scratch, n_streams, 0);
+  EntScratch s = ent_carve(d_scratch, n_streams, 0);
+  tic::EntRng* rng = RNG ? reinterpret_cast<tic::EntRng*>(s.seg_off) : nullptr;
+  s.seg_off = reinterpret_cast<unsigned long long*>(static_cast<uint8_t*>(d_scratch) + fixed);
   for (int f = 0; f < n_streams; f += tic::kEntStreams) {
     tic::EntChunk t;
     memset(&t, 0, sizeof(t));
@@ -1637,57 +1793,86 @@ int ent_decode(tic_handle* h, const uint8_t* d_blob, const int64_t* blob_offsets
       t.count[k] = counts[f + k];
       t.out_off[k] = sym_offsets[f + k];
     }
+    tic::EntRngChunk<RNG> rg;
+    if constexpr (RNG != 0) {
+      memset(&rg, 0, sizeof(rg));
+      for (int k = 0; k < t.n; ++k) rg.first[k] = firsts[f + k], rg.count[k] = rcounts[f + k];
+    }
     touch(h);
     if (nbr)
-      hipLaunchKernelGGL(tic::ent_dec_header_kernel<36>, dim3(1), dim3(64), 0, h->stream, t, d_blob, tb.K0, tb.crc, g0,
-                         g1, s.rec, s.aux);
+      hipLaunchKernelGGL((tic::ent_dec_header_kernel<36, RNG>), dim3(1), dim3(64), 0, h->stream,
+                         t, d_blob, tb.K0, tb.crc, g0,
+                         g1, s.rec, s.aux, rg, rng);
     else if (ctx)
-      hipLaunchKernelGGL(tic::ent_dec_header_kernel<28>, dim3(1), dim3(64), 0, h->stream, t, d_blob, tb.K, tb.crc, 0u,
-                         0u, s.rec, s.aux);
+      hipLaunchKernelGGL((tic::ent_dec_header_kernel<28, RNG>), dim3(1), dim3(64), 0, h->stream,
+                         t, d_blob, tb.K, tb.crc, 0u,
+                         0u, s.rec, s.aux, rg, rng);
     else
-      hipLaunchKernelGGL(tic::ent_dec_header_kernel<20>, dim3(1), dim3(64), 0, h->stream, t, d_blob, 0u, 0u, 0u, 0u,
-                         s.rec, s.aux);
+      hipLaunchKernelGGL((tic::ent_dec_header_kernel<20, RNG>), dim3(1), dim3(64), 0, h->stream,
+                         t, d_blob, 0u, 0u, 0u, 0u,
+                         s.rec, s.aux, rg, rng);
     if ((rc = check_launch())) return rc;
   }
   hipLaunchKernelGGL(tic::ent_stream_scan_kernel, dim3(1), dim3(256), 0, h->stream, (const unsigned long long*)s.aux,
                      n_streams, s.seg_base);
   if ((rc = check_launch())) return rc;
   const unsigned long long* seg_base = s.seg_base;
+  const tic::EntRng* crng = rng;
   if (nbr)
-    hipLaunchKernelGGL(tic::ent_dec_scan_kernel<36>, dim3((unsigned)n_streams), dim3(256), 0, h->stream, d_blob, s.rec,
-                       seg_base, cap, s.seg_off, d_sym);
+    hipLaunchKernelGGL((tic::ent_dec_scan_kernel<36, RNG>), dim3((unsigned)n_streams), dim3(256), 0, h->stream,
+                       d_blob, s.rec,
+                       seg_base, cap, s.seg_off, d_sym, crng);
   else if (ctx)
-    hipLaunchKernelGGL(tic::ent_dec_scan_kernel<28>, dim3((unsigned)n_streams), dim3(256), 0, h->stream, d_blob, s.rec,
-                       seg_base, cap, s.seg_off, d_sym);
+    hipLaunchKernelGGL((tic::ent_dec_scan_kernel<28, RNG>), dim3((unsigned)n_streams), dim3(256), 0, h->stream,
+                       d_blob, s.rec,
+                       seg_base, cap, s.seg_off, d_sym, crng);
   else
-    hipLaunchKernelGGL(tic::ent_dec_scan_kernel<20>, dim3((unsigned)n_streams), dim3(256), 0, h->stream, d_blob, s.rec,
-                       seg_base, cap, s.seg_off, d_sym);
+    hipLaunchKernelGGL((tic::ent_dec_scan_kernel<20, RNG>), dim3((unsigned)n_streams), dim3(256), 0, h->stream,
+                       d_blob, s.rec,
+                       seg_base, cap, s.seg_off, d_sym, crng);
   if ((rc = check_launch())) return rc;
-  const unsigned wgs = (unsigned)std::min<unsigned long long>((cap + 63) / 64, 1u << 16);
+  const unsigned wgs = (unsigned)std::min<unsigned long long>((cap + lanes - 1) / lanes, 1u << 16);
   const tic::EntRec* rec = s.rec;
   const unsigned long long* seg_off = s.seg_off;
   if (!ctx)
-    hipLaunchKernelGGL(tic::ent_decode_kernel, dim3(wgs), dim3(64), lds, h->stream, m, lut, d_blob, rec, seg_base,
-                       n_streams, seg_off, d_sym);
+    hipLaunchKernelGGL(tic::ent_decode_kernel<RNG>, dim3(wgs), dim3(64), lds, h->stream, m, lut, d_blob, rec, seg_base,
+                       n_streams, seg_off, d_sym, crng);
   else if (nbr && in_lds && ring)
-    hipLaunchKernelGGL((tic::ent_decode_nbr_kernel<1, 1>), dim3(wgs), dim3(64), lds, h->stream,
-                       (const uint32_t*)tb.d_tab, q, d_blob, rec, seg_base, n_streams, seg_off, d_sym);
+    hipLaunchKernelGGL((tic::ent_decode_nbr_kernel<1, 1, RNG>), dim3(wgs), dim3(64), lds, h->stream,
+                       (const uint32_t*)tb.d_tab, q, d_blob, rec, seg_base, n_streams, seg_off, d_sym, crng);
   else if (nbr && in_lds)
-    hipLaunchKernelGGL((tic::ent_decode_nbr_kernel<1, 0>), dim3(wgs), dim3(64), lds, h->stream,
-                       (const uint32_t*)tb.d_tab, q, d_blob, rec, seg_base, n_streams, seg_off, d_sym);
+    hipLaunchKernelGGL((tic::ent_decode_nbr_kernel<1, 0, RNG>), dim3(wgs), dim3(64), lds, h->stream,
+                       (const uint32_t*)tb.d_tab, q, d_blob, rec, seg_base, n_streams, seg_off, d_sym, crng);
   else if (nbr && ring)
-    hipLaunchKernelGGL((tic::ent_decode_nbr_kernel<0, 1>), dim3(wgs), dim3(64), lds, h->stream,
-                       (const uint32_t*)tb.d_tab, q, d_blob, rec, seg_base, n_streams, seg_off, d_sym);
+    hipLaunchKernelGGL((tic::ent_decode_nbr_kernel<0, 1, RNG>), dim3(wgs), dim3(64), lds, h->stream,
+                       (const uint32_t*)tb.d_tab, q, d_blob, rec, seg_base, n_streams, seg_off, d_sym, crng);
   else if (nbr)
-    hipLaunchKernelGGL((tic::ent_decode_nbr_kernel<0, 0>), dim3(wgs), dim3(64), lds, h->stream,
-                       (const uint32_t*)tb.d_tab, q, d_blob, rec, seg_base, n_streams, seg_off, d_sym);
+    hipLaunchKernelGGL((tic::ent_decode_nbr_kernel<0, 0, RNG>), dim3(wgs), dim3(64), lds, h->stream,
+                       (const uint32_t*)tb.d_tab, q, d_blob, rec, seg_base, n_streams, seg_off, d_sym, crng);
   else if (in_lds)
-    hipLaunchKernelGGL(tic::ent_decode_ctx_kernel<1>, dim3(wgs), dim3(64), lds, h->stream, (const uint32_t*)tb.d_tab,
-                       tb.K, tb.ncum, d_blob, rec, seg_base, n_streams, seg_off, d_sym);
+    hipLaunchKernelGGL((tic::ent_decode_ctx_kernel<1, RNG>), dim3(wgs), dim3(64), lds, h->stream,
+                       (const uint32_t*)tb.d_tab,
+                       tb.K, tb.ncum, d_blob, rec, seg_base, n_streams, seg_off, d_sym, crng);
   else
-    hipLaunchKernelGGL(tic::ent_decode_ctx_kernel<0>, dim3(wgs), dim3(64), 0, h->stream, (const uint32_t*)tb.d_tab,
-                       tb.K, tb.ncum, d_blob, rec, seg_base, n_streams, seg_off, d_sym);
+    hipLaunchKernelGGL((tic::ent_decode_ctx_kernel<0, RNG>), dim3(wgs), dim3(64), 0, h->stream,
+                       (const uint32_t*)tb.d_tab,
+                       tb.K, tb.ncum, d_blob, rec, seg_base, n_streams, seg_off, d_sym, crng);
   return check_launch();
+}
+
+
+int ent_decode(tic_handle* h, const uint8_t* d_blob, const int64_t* blob_offsets, const int64_t* blob_sizes,
+               const int64_t* counts, int n_streams, uint8_t* d_sym, const int64_t* sym_offsets, void* d_scratch,
+               size_t scratch_bytes, int ver) {
+  return ent_decode_t<0>(h, d_blob, blob_offsets, blob_sizes, counts, nullptr, nullptr, n_streams, d_sym, sym_offsets,
+                         d_scratch, scratch_bytes, ver);
+}
+
+int ent_decode_ranges(tic_handle* h, const uint8_t* d_blob, const int64_t* blob_offsets, const int64_t* blob_sizes,
+                      const int64_t* counts, const int64_t* firsts, const int64_t* rcounts, int n_ranges,
+                      uint8_t* d_sym, const int64_t* sym_offsets, void* d_scratch, size_t scratch_bytes, int ver) {
+  return ent_decode_t<1>(h, d_blob, blob_offsets, blob_sizes, counts, firsts, rcounts, n_ranges, d_sym, sym_offsets,
+                         d_scratch, scratch_bytes, ver);
 }
 
 }  // namespace

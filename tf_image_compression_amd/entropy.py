@@ -14,6 +14,9 @@ stream is coded under row ``k mod K`` (``K`` = the code's channel count: one tab
 ``K`` = the symbols of a patch: one per code position).  ``pack``, ``unpack`` and ``bound`` take
 either kind of table; ``parse`` reads version 1 only and ``parse_ctx`` version 2 only.
 
+``range_extent`` and ``unpack_range`` read a symbol range out of a container of any version: the
+segments that hold it and nothing else.
+
 A 3-D table ``[K0, M, ncum]`` selects the causal-neighbour model of version 3 and needs
 ``geometry=(eh, ew, C)``, the shape of the code the symbols are a patch-major sequence of:
 ``M`` = 3 conditions every symbol on the class of its W neighbour (one position to the left, same
@@ -221,3 +224,45 @@ def unpack(buf, cum_freq, n: int | None = None, geometry=None) -> np.ndarray:
     if rc:
         _raise(rc, "entropy.unpack")
     return out
+
+
+def range_extent(buf, first: int, count: int) -> tuple[int, int, int, int]:
+    """``(j0, nj, byte_off, byte_len)``: the segments ``j0 .. j0 + nj - 1`` that hold symbols
+    ``[first, first + count)`` of a container of any version, and the byte extent of their
+    payloads from the container's start.  ``buf`` needs to hold the header and the length table
+    only."""
+    if int(first) < 0 or int(count) < 0:
+        raise ValueError(f"symbol range [{first}, {first} + {count}) is negative")
+    a = np.frombuffer(bytes(buf), np.uint8)
+    out = [C.c_size_t() for _ in range(4)]
+    rc = lib().tic_rcseg_range_extent(_u8(a) if a.size else None, a.size, int(first), int(count),
+                                      *[C.byref(v) for v in out])
+    if rc:
+        _raise(rc, "entropy.range_extent")
+    return tuple(int(v.value) for v in out)
+
+
+def unpack_range(buf, cum_freq, first: int, count: int, geometry=None) -> np.ndarray:
+    """``unpack(buf, cum_freq, geometry=geometry)[first:first + count]`` decoding only the
+    segments that hold the range (no payload byte outside ``range_extent``'s extent is read).
+    The version follows the table's rank as in ``unpack``, with the same checks."""
+    if int(first) < 0 or int(count) < 0:
+        raise ValueError(f"symbol range [{first}, {first} + {count}) is negative")
+    ctx, nbr = is_ctx_table(cum_freq), is_nbr_table(cum_freq)
+    table = nbr_tables(cum_freq) if nbr else ctx_tables(cum_freq) if ctx else _table(cum_freq)
+    a = np.frombuffer(bytes(buf), np.uint8)
+    n = parse_nbr(a)[1] if nbr else parse_ctx(a)[1] if ctx else parse(a)[1]
+    out = np.empty(max(int(count), 1), np.uint8)
+    pa = _u8(a) if a.size else None
+    if nbr:
+        eh, ew, c = _geometry(geometry)
+        rc = lib().tic_rcseg_decode_range_nbr(pa, a.size, _i64(table), table.shape[0], neighbours_of(table),
+                                              table.shape[2], eh, ew, c, _u8(out), n, int(first), int(count))
+    elif ctx:
+        rc = lib().tic_rcseg_decode_range_ctx(pa, a.size, _i64(table), table.shape[0], table.shape[1], _u8(out), n,
+                                              int(first), int(count))
+    else:
+        rc = lib().tic_rcseg_decode_range(pa, a.size, _i64(table), table.size, _u8(out), n, int(first), int(count))
+    if rc:
+        _raise(rc, "entropy.unpack_range")
+    return out[:int(count)]

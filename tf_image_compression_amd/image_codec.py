@@ -368,12 +368,11 @@ class ImageCodec:
         cuts = np.cumsum(nbytes.astype(np.int64))[:-1]
         return [part.tobytes() for part in np.split(blob, cuts)]
 
-    def decode_streams_to_images(self, streams, sizes, cum_freq, post_filter: bool = True) -> list[np.ndarray]:
-        """[container], [(H_i, W_i)] -> [uint8 [H_i, W_i, 3]]: every container is validated on the
-        host (entropy.parse) and its symbol count checked against the image size and the code
-        shape; then one upload, one decoder call for all of them and ``decode_images_device``.  A 2-D
-        ``cum_freq`` reads version-2 containers, which must have been coded under these tables; a
-        3-D one version-3 containers coded under these tables for this codec's code shape."""
+    def _check_streams(self, streams, sizes, cum_freq):
+        """The host validation of ``decode_streams_to_images`` and ``decode_regions``: every
+        container parsed as the version the table's rank selects, its K / K0, geometry, neighbours
+        and CRC against the tables, its symbol count against the image size and the code shape.
+        ``(version, tables, sizes, counts, min_L)``; tables is None for version 1."""
         from . import entropy
         ctx, nbr = entropy.is_ctx_table(cum_freq), entropy.is_nbr_table(cum_freq)
         if nbr:
@@ -386,10 +385,7 @@ class ImageCodec:
         sizes = [(int(H), int(W)) for H, W in sizes]
         if len(streams) != len(sizes):
             raise ValueError(f"{len(streams)} streams for {len(sizes)} image sizes")
-        if not sizes:
-            return []
-        c = self.codec
-        code = int(np.prod(c.code_shape))
+        code = int(np.prod(self.codec.code_shape))
         counts, min_L = [], 16384
         for i, (buf, (H, W)) in enumerate(zip(streams, sizes)):
             if H <= 0 or W <= 0:
@@ -412,6 +408,19 @@ class ImageCodec:
                 raise ValueError(f"stream {i} holds {n} symbols, a {H}x{W} image has {want}")
             counts.append(n)
             min_L = min(min_L, L)
+        return (3 if nbr else 2 if ctx else 1), (tables if ctx or nbr else None), sizes, counts, min_L
+
+    def decode_streams_to_images(self, streams, sizes, cum_freq, post_filter: bool = True) -> list[np.ndarray]:
+        """[container], [(H_i, W_i)] -> [uint8 [H_i, W_i, 3]]: every container is validated on the
+        host (entropy.parse) and its symbol count checked against the image size and the code
+        shape; then one upload, one decoder call for all of them and ``decode_images_device``.  A 2-D
+        ``cum_freq`` reads version-2 containers, which must have been coded under these tables; a
+        3-D one version-3 containers coded under these tables for this codec's code shape."""
+        ver, tables, sizes, counts, min_L = self._check_streams(streams, sizes, cum_freq)
+        if not sizes:
+            return []
+        ctx, nbr = ver >= 2, ver == 3
+        c = self.codec
         blob = np.frombuffer(b"".join(bytes(b) for b in streams), np.uint8)
         bsizes = [len(b) for b in streams]
         boffs = np.concatenate([[0], np.cumsum(bsizes)[:-1]]).astype(np.int64)
@@ -434,6 +443,135 @@ class ImageCodec:
         self.synchronize()
         flat = d_out.download((total,), np.uint8)
         return [flat[o:o + H * W * 3].reshape(H, W, 3).copy() for o, (H, W) in zip(offsets, sizes)]
+
+    # ------------------------------------------------------------------ regions
+    # A rectangle of an image from a small part of its container: patches are independent and so
+    # are the segments of a container, so the crop needs the patches it touches (and, with the
+    # post-filter, those its windows reach: tic_region_plan) and those patches' symbols need the
+    # segments that hold them and nothing else (tic_entropy_decode_ranges*_device).
+    RMBE_WINDOW = 128  # the post-filter's window side (submit/2/rmbe/rmbe.py:12)
+
+    def region_plan(self, size, region, post_filter: bool = True) -> tuple[int, int, int, int]:
+        """``(py0, py1, px0, px1)``: the box of patches the region ``(y, x, h, w)`` of an image of
+        ``size = (H, W)`` is decoded from; with the post-filter (and a ``post`` codec) widened over
+        the windows the region's pixels depend on.  ValueError for a region that is empty or not
+        inside the image."""
+        H, W = (int(v) for v in size)
+        y, x, h, w = (int(v) for v in region)
+        S = self.RMBE_WINDOW if post_filter and self.post is not None else 0
+        return Codec.region_plan(H, W, self.codec.patch_size, y, x, h, w, S)
+
+    @staticmethod
+    def _merge_extents(extents):
+        """Byte extents [(offset, length)] merged where they overlap or touch, sorted."""
+        out: list[list[int]] = []
+        for lo, ln in sorted((int(o), int(n)) for o, n in extents if n > 0):
+            if out and lo <= out[-1][1]:
+                out[-1][1] = max(out[-1][1], lo + ln)
+            else:
+                out.append([lo, lo + ln])
+        return [(lo, hi - lo) for lo, hi in out]
+
+    def decode_regions(self, streams, sizes, regions, cum_freq, post_filter: bool = True) -> list[np.ndarray]:
+        """[container], [(H_i, W_i)], [(y_i, x_i, h_i, w_i)] -> [uint8 [h_i, w_i, 3]]: the bytes of
+        ``decode_streams_to_images(...)[i][y:y + h, x:x + w]`` from the patches of ``region_plan``'s
+        box only.  Validation as ``decode_streams_to_images`` does it.  For every grid row of a box
+        its patches are one contiguous symbol range, and the ranges' outputs laid back to back are
+        the patch batch of the boxes.  Only the header, the length table and the byte extents of
+        those ranges (entropy.range_extent, overlapping ones merged) are copied to the device, at
+        their container offsets; the rest of the device buffer is left as it was.  Then one range
+        decoder call, one decoder call, one stitch, the region post-filter on the post-filter's
+        stream, one rounding, the crops and one download.  ``last_region_stats`` holds, per
+        stream, the patches decoded and the bytes uploaded."""
+        from . import entropy
+        ver, tables, sizes, counts, min_L = self._check_streams(streams, sizes, cum_freq)
+        if len(regions) != len(sizes):
+            raise ValueError(f"{len(regions)} regions for {len(sizes)} images")
+        if not sizes:
+            return []
+        c = self.codec
+        P = c.patch_size
+        code = int(np.prod(c.code_shape))
+        use_post = post_filter and self.post is not None
+        hdr = {1: entropy.HEADER_BYTES, 2: entropy.HEADER_BYTES_CTX, 3: entropy.HEADER_BYTES_NBR}[ver]
+        regions = [tuple(int(v) for v in r) for r in regions]
+        bsizes = [len(b) for b in streams]
+        boffs = np.concatenate([[0], np.cumsum(bsizes)[:-1]]).astype(np.int64)
+        # per range (one per grid row of a box): its container, first symbol and symbol count
+        r_stream, r_first, r_count = [], [], []
+        boxes, origins, crops, pieces, stats = [], [], [], [], []
+        for i, ((H, W), (y, x, h, w), buf) in enumerate(zip(sizes, regions, streams)):
+            py0, py1, px0, px1 = self.region_plan((H, W), (y, x, h, w), post_filter)
+            wn = self.grid(H, W)[1]
+            L = int.from_bytes(bytes(buf[8:12]), "little")  # validated above
+            head = bytes(buf[:hdr + 2 * -(-counts[i] // L)])
+            extents = []
+            for py in range(py0, py1):
+                first, count = (py * wn + px0) * code, (px1 - px0) * code
+                r_stream.append(i), r_first.append(first), r_count.append(count)
+                extents.append(entropy.range_extent(head, first, count)[2:])
+            merged = self._merge_extents(extents)
+            pieces += [(int(boffs[i]), head)] + [(int(boffs[i]) + o, bytes(buf[o:o + ln])) for o, ln in merged]
+            boxes.append((min(py1 * P, H) - py0 * P, min(px1 * P, W) - px0 * P))
+            origins.append((py0 * P, px0 * P))
+            crops.append((y - py0 * P, x - px0 * P))
+            stats.append({"patches": (py1 - py0) * (px1 - px0), "patches_image": self.num_patches(H, W),
+                          "bytes_uploaded": len(head) + sum(ln for _, ln in merged), "bytes_container": len(buf)})
+        self.last_region_stats = stats
+        n_box = sum(s["patches"] for s in stats)
+        if ver == 3:
+            c.entropy_set_tables_nbr(tables)
+        elif ver == 2:
+            c.entropy_set_tables(tables)
+        else:
+            c.entropy_set_table(cum_freq)
+        d_blob = self._buf("entropy_blob", int(sum(bsizes)))
+        for at, data in pieces:  # the sparse upload: everything else in d_blob stays as it was
+            d_blob.view(at).upload(np.frombuffer(data, np.uint8))
+        d_scr = self._buf("entropy_scratch", c.entropy_ranges_scratch_bytes(r_first, r_count, min_L))
+        d_sym = self._buf("symbols", n_box * code)
+        soffs = np.concatenate([[0], np.cumsum(r_count)[:-1]]).astype(np.int64)
+        c.entropy_decode_ranges_device(d_blob, [boffs[i] for i in r_stream], [bsizes[i] for i in r_stream],
+                                       [counts[i] for i in r_stream], r_first, r_count, d_sym, soffs, d_scr,
+                                       version=ver)
+        # the boxes are the images of a group: decode_images_device's steps with the region filter
+        offsets, total = self.packed_offsets(boxes)
+        runs = self._runs(offsets, boxes)
+        d_f = self._buf("patches_f32", n_box * P * P * 3 * 4)
+        d_u8 = self._buf("image_out", total)
+        out_sizes = [(h, w) for _, _, h, w in regions]
+        out_offs, out_total = self.packed_offsets(out_sizes)
+        d_crop = self._buf("region_out", out_total)
+        if use_post:
+            k = self._slot
+            self._slot = (k + 1) % self.NSLOT
+            self.last_slot = k
+            d_img = self._buf(f"image_f32_{k}", total * 4)
+            c.decode_device(d_sym, n_box, None, d_f)
+            c.wait_event(self.post, k)
+            c.patches_to_images_device(d_f, offsets, boxes, P, d_img)
+            c.record(k)
+            self.post.wait_event(c, k)
+            self.post.rmbe_regions_device(d_img, offsets, boxes, origins, sizes)
+            last = self.post
+        else:
+            d_img = self._buf("image_f32_0", total * 4)
+            if self.post is not None:
+                c.wait_event(self.post, 0)
+            c.decode_device(d_sym, n_box, None, d_f)
+            c.patches_to_images_device(d_f, offsets, boxes, P, d_img)
+            last = c
+        for lo, ln in runs:
+            last.round_u8_device(d_img.view(lo * 4), ln, d_u8.view(lo))
+        last.crop_regions_device(d_u8, offsets, boxes, crops, out_sizes, out_offs, d_crop)
+        if use_post:
+            self.post.record(k)
+        elif self.post is not None:
+            c.record(0)
+            self.post.wait_event(c, 0)
+        self.synchronize()
+        flat = d_crop.download((out_total,), np.uint8)
+        return [flat[o:o + h * w * 3].reshape(h, w, 3).copy() for o, (h, w) in zip(out_offs, out_sizes)]
 
     # ------------------------------------------------------------------ rate / distortion
     def evaluate_images(self, images, post_filter: bool = True, cum_freq=None,
