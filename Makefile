@@ -7,7 +7,7 @@ BUILD    := build
 LIB      := tf_image_compression_amd/libtic.so
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -Iinclude -I$(CSRC)
 KERNELS  := conv_s1 conv_s2 conv_t2 conv_rgb conv_chain image_ops
-OBJS     := $(addprefix $(BUILD)/,$(addsuffix .o,$(KERNELS))) $(BUILD)/tic_region.o $(BUILD)/range_coder.o \
+OBJS     := $(addprefix $(BUILD)/,$(addsuffix .o,$(KERNELS))) $(BUILD)/tic_entropy_emb.o $(BUILD)/range_coder.o \
             $(BUILD)/host_util.o
 HDRS     := $(wildcard $(CSRC)/*.h) include/tic.h
 
@@ -16,12 +16,13 @@ all: $(LIB)
 $(BUILD)/%.o: $(CSRC)/%.hip $(HDRS) | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-# tic_region.cpp includes tic_entropy.cpp, which includes tic_msssim.cpp, which includes
-# tic_image_batch.cpp, which includes tic_runtime.cpp: the host runtime, the image-list entries, the
-# MS-SSIM entries, the entropy coder and the region entries are one translation unit (the entries
-# use the handle's internals; tic_runtime.cpp itself stays as the shipped tuning states were stamped)
-$(BUILD)/tic_region.o: $(CSRC)/tic_region.cpp $(CSRC)/tic_entropy.cpp $(CSRC)/tic_msssim.cpp \
-                       $(CSRC)/tic_image_batch.cpp $(CSRC)/tic_runtime.cpp $(HDRS) | $(BUILD)
+# tic_entropy_emb.cpp includes tic_region.cpp, which includes tic_entropy.cpp, which includes
+# tic_msssim.cpp, which includes tic_image_batch.cpp, which includes tic_runtime.cpp: the host
+# runtime, the image-list entries, the MS-SSIM entries, the entropy coders and the region entries
+# are one translation unit (the entries use the handle's internals; tic_runtime.cpp itself stays as
+# the shipped tuning states were stamped)
+$(BUILD)/tic_entropy_emb.o: $(CSRC)/tic_entropy_emb.cpp $(CSRC)/tic_region.cpp $(CSRC)/tic_entropy.cpp \
+                            $(CSRC)/tic_msssim.cpp $(CSRC)/tic_image_batch.cpp $(CSRC)/tic_runtime.cpp $(HDRS) | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
 
 $(BUILD)/range_coder.o: $(CSRC)/range_coder.cpp include/tic.h | $(BUILD)
@@ -82,7 +83,16 @@ $(RCSEG_RANGE_BIN): tests/native/rcseg_range_fuzz.cpp $(CSRC)/range_coder.cpp $(
 	g++ -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=all \
 	    -Iinclude -o $@ tests/native/rcseg_range_fuzz.cpp $(CSRC)/range_coder.cpp $(CSRC)/host_util.cpp
 
+# The embedded-table ("TICA") container entries (tic_rcseg_count_nbr, _fit_tables, tic_rcseg_*_emb).
+RCSEG_EMB_BIN := $(BUILD)/rcseg_emb_fuzz_asan
+asan-rcseg-emb: $(RCSEG_EMB_BIN)
+	$(RCSEG_EMB_BIN)
+
+$(RCSEG_EMB_BIN): tests/native/rcseg_emb_fuzz.cpp $(CSRC)/range_coder.cpp $(CSRC)/host_util.cpp include/tic.h | $(BUILD)
+	g++ -O1 -g -std=c++17 -Wall -fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=all \
+	    -Iinclude -o $@ tests/native/rcseg_emb_fuzz.cpp $(CSRC)/range_coder.cpp $(CSRC)/host_util.cpp
+
 clean:
 	rm -rf $(BUILD) $(LIB)
 
-.PHONY: all clean asan asan-rcseg asan-rcseg-ctx asan-rcseg-nbr asan-rcseg-range
+.PHONY: all clean asan asan-rcseg asan-rcseg-ctx asan-rcseg-nbr asan-rcseg-range asan-rcseg-emb

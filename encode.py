@@ -15,7 +15,9 @@ no checkpoint exists), ``--raw`` (store bit-packed symbols, no entropy coding),
 ``--batch-images N`` (N > 1: consecutive images share one patch batch, image_codec.py),
 ``--entropy device`` (the symbols stay on the GPU and are range-coded there, one segment of
 ``--segment L`` symbols per lane; each file then holds one segmented-stream container,
-tf_image_compression_amd/entropy.py, which ``decode.py --entropy device`` reads).  With
+tf_image_compression_amd/entropy.py, which ``decode.py --entropy device`` reads;
+``--tables adaptive`` or ``auto`` fits the tables to every image and stores them in its file, so
+no ``--dist`` is read here or by the decoder).  With
 ``--entropy device`` a 2-D ``--dist`` array ([K, Q] per-context probabilities,
 get_encoded_distribution.py --context) codes symbol k of an image under table k mod K and writes
 version-2 containers.  A 3-D array ([K0, M, Q], get_encoded_distribution.py --context --neighbours)
@@ -61,9 +63,19 @@ def my_parse_args(argv=None):
                         "range-code on the GPU into one segmented-stream container per file")
     p.add_argument("--segment", type=int, default=2048, metavar="L",
                    help="symbols per segment of --entropy device (multiple of 4, 4..16384)")
+    p.add_argument("--tables", choices=["dist", "adaptive", "auto"], default="dist",
+                   help="with --entropy device: dist (the default) codes under the --dist array; adaptive fits the "
+                        "tables of --context / --neighbours to every image and writes them into its file, which "
+                        "then decodes without any --dist; auto also chooses the model per image")
+    p.add_argument("--context", choices=["none", "channel"], default="channel",
+                   help="--tables adaptive: one table (none) or one per channel of the code (channel)")
+    p.add_argument("--neighbours", type=int, choices=[0, 1, 2], default=0,
+                   help="--tables adaptive: also condition on the class of the W neighbour (1) or of W and N (2)")
     args = p.parse_args(argv)
     if args.entropy == "device" and args.raw:
         p.error("--raw stores symbols without entropy coding: it cannot be combined with --entropy device")
+    if args.tables != "dist" and args.entropy != "device":
+        p.error("--tables adaptive / auto writes segmented-stream containers: it needs --entropy device")
     if args.entropy == "host" and not args.raw:
         from tf_image_compression_amd.range_coder import dist_is_ctx
         if dist_is_ctx(args.dist.format(args.model_num)):
@@ -118,7 +130,11 @@ def compress(model, args):
     codec = model.codec(P, Q)
     from tf_image_compression_amd.image_codec import ImageCodec
     ic = ImageCodec(codec)
-    cum_freq = None if args.raw else symbol_table(args, config)
+    if args.tables != "dist":  # no --dist file is read: the tables come from every image itself
+        from tf_image_compression_amd.entropy import Adaptive
+        cum_freq = Adaptive.auto(Q) if args.tables == "auto" else Adaptive(args.context, args.neighbours, Q)
+    else:
+        cum_freq = None if args.raw else symbol_table(args, config)
     out_dir = args.output_dir.format(args.model_num)
     os.makedirs(out_dir, exist_ok=True)
     t0 = time.time()

@@ -57,9 +57,17 @@ def my_parse_args(argv=None):
                         "print the real coded_bytes and the bpp from them beside the estimate")
     p.add_argument("--segment", type=int, default=2048, metavar="L",
                    help="symbols per segment of --entropy device (multiple of 4, 4..16384)")
+    p.add_argument("--tables", choices=["dist", "adaptive", "auto"], default="dist",
+                   help="with --entropy device: dist (the default) codes under the --dist array; adaptive fits the "
+                        "tables of --context / --neighbours to every image and counts them in coded_bytes (no --dist "
+                        "is read, no estimate is printed); auto also chooses the model per image")
+    p.add_argument("--context", choices=["none", "channel"], default="channel")
+    p.add_argument("--neighbours", type=int, choices=[0, 1, 2], default=0)
     args = p.parse_args(argv)
     if args.batch_images < 1:
         p.error("--batch-images must be at least 1")
+    if args.tables != "dist" and args.entropy != "device":
+        p.error("--tables adaptive / auto needs --entropy device")
     if args.entropy == "host":
         from tf_image_compression_amd.range_coder import dist_is_ctx
         if dist_is_ctx(args.dist.format(args.model_num)):
@@ -113,7 +121,10 @@ def run(model, args) -> dict:
     codec = model.codec(P, Q)
     cum_freq = None
     dist = args.dist.format(args.model_num)
-    if os.path.exists(dist):
+    if getattr(args, "tables", "dist") != "dist":
+        from tf_image_compression_amd.entropy import Adaptive
+        cum_freq = Adaptive.auto(Q) if args.tables == "auto" else Adaptive(args.context, args.neighbours, Q)
+    elif os.path.exists(dist):
         from tf_image_compression_amd.range_coder import dist_table
         cum_freq = dist_table(np.load(dist, allow_pickle=False), resolution=config["resolution"])
         if np.ndim(cum_freq) >= 2 and getattr(args, "entropy", "host") != "device":

@@ -459,6 +459,59 @@ int tic_rcseg_decode_range_nbr(const uint8_t* buf, size_t nbytes, const int64_t*
                                uint32_t neighbours, size_t ncum, uint32_t eh, uint32_t ew, uint32_t C,
                                uint8_t* sym_out, size_t n, size_t first, size_t count);
 
+/* --- "TICA" version 1: a segmented stream that carries its own tables (host part) ---
+ * Version 3's context model under tables fitted to the stream itself (semi-static two-pass
+ * coding), so a decoder needs nothing but the container.  All integers little-endian:
+ *    0 4  magic "TICA"               20 4  K0 (>= 1)
+ *    4 1  version = 1                24 6  u16 eh, u16 ew, u16 C (each 1..65535)
+ *    5 1  neighbours in {0, 1, 2}    30 2  zero
+ *    6 2  nsym (2..256)              32 4  T = K0*M*(nsym-1)*2, the bytes of the table block
+ *    8 4  L (multiple of 4, 4..16384) 36 4 CRC-32C (tic_crc32c) of the T table-block bytes
+ *   12 8  n (> 0)                    40 T  table block
+ *   40+T  the u16 payload length of each of the S = ceil(n/L) segments, then the S payloads
+ * M = 3^neighbours.  The row of symbol k is version 3's (k mod K0)*M + nb, nb derived as above
+ * (neighbours only inside the symbol's own segment, class(s) = 2*s >= nsym) and 0 when
+ * neighbours = 0.  K0*M*(nsym+1) <= 262144.
+ * Table block: rows r = 0 .. K0*M - 1, each nsym - 1 u16 frequencies f_0 .. f_{nsym-2}; the last
+ * frequency is 4096 minus their sum.  Every frequency, the implied one included, is >= 1 and every
+ * row's total is 4096.
+ * Payloads: as versions 2 and 3, what tic_rc_encode writes with one call per symbol under the row's
+ * cumulative table.  Length table and payloads are therefore byte for byte those of a version-3
+ * container packed with the same tables, geometry and L (neighbours = 0: of a version-2 container
+ * with K = K0).
+ * Fit rule (integers only): a row's counts c_0 .. c_{nsym-1} are taken over the whole stream at
+ * the container's L; n_r is their sum.  n_r = 0: f_s = floor(4096*(s+1)/nsym) - floor(4096*s/nsym).
+ * Otherwise f_s = 1 + floor(c_s*(4096 - nsym)/n_r) in 64-bit arithmetic, and the deficit
+ * 4096 - sum f_s (0 <= deficit < nsym) is added to the symbol with the largest count, the lowest
+ * index on ties.
+ * The "TICS" entries above reject these containers (another magic), and these reject "TICS". */
+
+/* counts[K0*M][nsym] (overwritten): symbol k of sym[0..n) counts in row (k mod K0)*M + nb at
+ * segment length L.  TIC_EINVAL for a symbol >= nsym or a model outside the limits. */
+int tic_rcseg_count_nbr(const uint8_t* sym, size_t n, uint32_t L, size_t K0, uint32_t neighbours, size_t nsym,
+                        uint32_t eh, uint32_t ew, uint32_t C, uint64_t* counts);
+/* The fit rule: counts[K][nsym] (each at most 2^40) to cumulative tables[K][nsym + 1], totals 4096. */
+int tic_rcseg_fit_tables(const uint64_t* counts, size_t K, size_t nsym, int64_t* tables);
+/* tic_rcseg_bound + 20 + T. */
+int tic_rcseg_bound_emb(size_t n, uint32_t L, size_t K0, uint32_t neighbours, size_t nsym, size_t* bytes);
+/* Count, fit, write: the container of sym[0..n).  cap >= tic_rcseg_bound_emb. */
+int tic_rcseg_encode_emb(const uint8_t* sym, size_t n, uint32_t L, size_t K0, uint32_t neighbours, size_t nsym,
+                         uint32_t eh, uint32_t ew, uint32_t C, uint8_t* out, size_t cap, size_t* written);
+/* Validates everything: magic, version, the zero bytes, the limits, T against its formula, the
+ * CRC, every frequency >= 1 with row sums <= 4095, and the length table as tic_rcseg_parse does.
+ * Outputs may be NULL; tables, when given, receives the K0*M cumulative rows [nsym + 1]. */
+int tic_rcseg_parse_emb(const uint8_t* buf, size_t nbytes, uint32_t* L, uint64_t* n, uint32_t* K0, uint32_t* eh,
+                        uint32_t* ew, uint32_t* C, uint32_t* neighbours, uint32_t* nsym, int64_t* tables);
+/* tic_rcseg_parse_emb, TIC_EINVAL when n differs from the header's, then the n symbols.  No table
+ * argument: the container's own. */
+int tic_rcseg_decode_emb(const uint8_t* buf, size_t nbytes, uint8_t* sym_out, size_t n);
+/* tic_rcseg_range_extent for a "TICA" container; needs only the bytes [0, 40 + T + 2S). */
+int tic_rcseg_range_extent_emb(const uint8_t* buf, size_t nbytes, size_t first, size_t count, size_t* j0, size_t* nj,
+                               size_t* byte_off, size_t* byte_len);
+/* tic_rcseg_decode_range for a "TICA" container; reads no payload byte outside the extent. */
+int tic_rcseg_decode_range_emb(const uint8_t* buf, size_t nbytes, uint8_t* sym_out, size_t n, size_t first,
+                               size_t count);
+
 /* --- segmented streams on the device (csrc/tic_entropy.cpp) ---
  * One range coder per lane, one segment each; a scan over the segment lengths; a gather that
  * writes the containers.  All entries are asynchronous on the handle's stream, never synchronise,
@@ -583,6 +636,59 @@ int tic_entropy_decode_ranges_nbr_device(tic_handle* h, const uint8_t* d_blob, c
                                          const int64_t* blob_sizes, const int64_t* stream_counts,
                                          const int64_t* firsts, const int64_t* counts, int n_ranges, uint8_t* d_sym,
                                          const int64_t* sym_offsets, void* d_scratch, size_t scratch_bytes);
+
+/* --- "TICA" streams on the device (csrc/tic_entropy_emb.cpp) ---
+ * One model (K0, neighbours, nsym, eh, ew, C) per call, tables per stream.  The model comes with
+ * every call: no tic_entropy_set_* call is needed and the handle's tables are left alone.  As the
+ * entries above: asynchronous on the handle's stream, no call synchronises, HOST arrays are read
+ * during the call only, TIC_EINVAL with nothing launched for what the version-3 entries reject and
+ * for a model outside the format's limits; n_streams == 0 does nothing.  Deterministic: the
+ * counters are integers, and no atomic decides an output byte otherwise. */
+
+/* Symbol k of stream i (counts[i] symbols at d_sym + sym_offsets[i]) counts in row
+ * (k mod K0)*M + nb of the uint64 counts d_counts[n_streams][K0*M][nsym] (8-byte aligned), nb as
+ * the coder derives it at segment length L.  A symbol >= nsym counts nowhere; as a neighbour its
+ * class is 1.  Accumulates (zero the counts first); integer adds only.  A workgroup counts in LDS
+ * when a stream's counts fit 32 KiB and adds its counts to the stream's once. */
+int tic_histogram_streams_nbr_device(tic_handle* h, const uint8_t* d_sym, const int64_t* sym_offsets,
+                                     const int64_t* counts, int n_streams, size_t nsym, uint32_t L, size_t K0,
+                                     uint32_t neighbours, uint32_t eh, uint32_t ew, uint32_t C, uint64_t* d_counts);
+/* Device scratch (bytes) tic_entropy_encode_emb_device and tic_entropy_decode_emb_device need for
+ * streams of these symbol counts at segment length L (decode: the smallest L of the containers).
+ * Host arithmetic only. */
+int tic_entropy_emb_scratch_bytes(const int64_t* counts, int n_streams, uint32_t L, size_t K0, uint32_t neighbours,
+                                  size_t nsym, size_t* bytes);
+/* tic_entropy_encode_nbr_device writing "TICA" containers, byte for byte tic_rcseg_encode_emb's:
+ * per-stream counts, the fit (one thread per row) and the per-stream cumulative tables live in the
+ * scratch; the segment coder reads its stream's tables (every stream gets whole workgroups, which
+ * stage the tables in LDS when K0*M*(nsym+1)*4 <= 64 KiB and read them from the scratch
+ * otherwise); the gather writes header, table block, CRC, length table and payloads.  out_cap at
+ * least the sum of tic_rcseg_bound_emb; d_sizes[i] = UINT64_MAX for a stream with a symbol >= nsym. */
+int tic_entropy_encode_emb_device(tic_handle* h, const uint8_t* d_sym, const int64_t* sym_offsets,
+                                  const int64_t* counts, int n_streams, uint32_t L, size_t K0, uint32_t neighbours,
+                                  size_t nsym, uint32_t eh, uint32_t ew, uint32_t C, void* d_scratch,
+                                  size_t scratch_bytes, uint8_t* d_out, size_t out_cap, uint64_t* d_sizes);
+/* tic_entropy_decode_nbr_device for "TICA" containers.  Every header is checked against the
+ * model given, counts[i] and blob_sizes[i], and the cumulative tables are rebuilt from the table
+ * block into the scratch.  A container that disagrees decodes to zeros, as one whose table block
+ * has a zero frequency or a row sum above 4095, fails its CRC or does not lie inside
+ * blob_sizes[i].  Reads stay inside each container whatever it holds; exactly counts[i] symbols
+ * below nsym are written. */
+int tic_entropy_decode_emb_device(tic_handle* h, const uint8_t* d_blob, const int64_t* blob_offsets,
+                                  const int64_t* blob_sizes, const int64_t* counts, int n_streams, size_t K0,
+                                  uint32_t neighbours, size_t nsym, uint32_t eh, uint32_t ew, uint32_t C, uint8_t* d_sym,
+                                  const int64_t* sym_offsets, void* d_scratch, size_t scratch_bytes);
+/* tic_entropy_ranges_scratch_bytes / tic_entropy_decode_ranges_nbr_device for "TICA" containers:
+ * one range per record (every record rebuilds its container's tables).  Only the bytes
+ * [0, 40 + T + 2S) of a container and the payloads of the range's segments are read. */
+int tic_entropy_ranges_emb_scratch_bytes(const int64_t* firsts, const int64_t* counts, int n_ranges, uint32_t L,
+                                         size_t K0, uint32_t neighbours, size_t nsym, size_t* bytes);
+int tic_entropy_decode_ranges_emb_device(tic_handle* h, const uint8_t* d_blob, const int64_t* blob_offsets,
+                                         const int64_t* blob_sizes, const int64_t* stream_counts,
+                                         const int64_t* firsts, const int64_t* counts, int n_ranges, size_t K0,
+                                         uint32_t neighbours, size_t nsym, uint32_t eh, uint32_t ew, uint32_t C,
+                                         uint8_t* d_sym, const int64_t* sym_offsets, void* d_scratch,
+                                         size_t scratch_bytes);
 
 /* --- a region of an image (csrc/tic_region.cpp) ---
  * Patches are independent and, in a segmented stream, so are the symbols of different segments:

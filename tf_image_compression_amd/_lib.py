@@ -153,6 +153,38 @@ SIGNATURES = [
 ] + [(name, C.c_int, [vp, vp] + [C.POINTER(C.c_int64)] * 5 + [C.c_int, vp, C.POINTER(C.c_int64), vp, C.c_size_t])
      for name in ("tic_entropy_decode_ranges_device", "tic_entropy_decode_ranges_ctx_device",
                   "tic_entropy_decode_ranges_nbr_device")] + [
+    # "TICA": a segmented stream that carries tables fitted to itself, host reference
+    ("tic_rcseg_count_nbr", C.c_int, [u8p, C.c_size_t, C.c_uint32, C.c_size_t, C.c_uint32, C.c_size_t, C.c_uint32,
+                                     C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64)]),
+    ("tic_rcseg_fit_tables", C.c_int, [C.POINTER(C.c_uint64), C.c_size_t, C.c_size_t, C.POINTER(C.c_int64)]),
+    ("tic_rcseg_bound_emb", C.c_int, [C.c_size_t, C.c_uint32, C.c_size_t, C.c_uint32, C.c_size_t,
+                                     C.POINTER(C.c_size_t)]),
+    ("tic_rcseg_encode_emb", C.c_int, [u8p, C.c_size_t, C.c_uint32, C.c_size_t, C.c_uint32, C.c_size_t, C.c_uint32,
+                                      C.c_uint32, C.c_uint32, u8p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("tic_rcseg_parse_emb", C.c_int, [u8p, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+                                     + [C.POINTER(C.c_uint32)] * 6 + [C.POINTER(C.c_int64)]),
+    ("tic_rcseg_decode_emb", C.c_int, [u8p, C.c_size_t, u8p, C.c_size_t]),
+    ("tic_rcseg_range_extent_emb", C.c_int, [u8p, C.c_size_t, C.c_size_t, C.c_size_t] + [C.POINTER(C.c_size_t)] * 4),
+    ("tic_rcseg_decode_range_emb", C.c_int, [u8p, C.c_size_t, u8p, C.c_size_t, C.c_size_t, C.c_size_t]),
+    # ... and on the device: the model (K0, neighbours, nsym, eh, ew, C) comes with every call
+    ("tic_histogram_streams_nbr_device", C.c_int, [vp, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int,
+                                                  C.c_size_t, C.c_uint32, C.c_size_t, C.c_uint32, C.c_uint32,
+                                                  C.c_uint32, C.c_uint32, vp]),
+    ("tic_entropy_emb_scratch_bytes", C.c_int, [C.POINTER(C.c_int64), C.c_int, C.c_uint32, C.c_size_t, C.c_uint32,
+                                               C.c_size_t, C.POINTER(C.c_size_t)]),
+    ("tic_entropy_encode_emb_device", C.c_int, [vp, vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int,
+                                               C.c_uint32, C.c_size_t, C.c_uint32, C.c_size_t, C.c_uint32,
+                                               C.c_uint32, C.c_uint32, vp, C.c_size_t, vp, C.c_size_t, vp]),
+    ("tic_entropy_decode_emb_device", C.c_int, [vp, vp] + [C.POINTER(C.c_int64)] * 3
+                                               + [C.c_int, C.c_size_t, C.c_uint32, C.c_size_t, C.c_uint32, C.c_uint32,
+                                                  C.c_uint32, vp, C.POINTER(C.c_int64), vp, C.c_size_t]),
+    ("tic_entropy_ranges_emb_scratch_bytes", C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int,
+                                                      C.c_uint32, C.c_size_t, C.c_uint32, C.c_size_t,
+                                                      C.POINTER(C.c_size_t)]),
+    ("tic_entropy_decode_ranges_emb_device", C.c_int, [vp, vp] + [C.POINTER(C.c_int64)] * 5
+                                                      + [C.c_int, C.c_size_t, C.c_uint32, C.c_size_t, C.c_uint32,
+                                                         C.c_uint32, C.c_uint32, vp, C.POINTER(C.c_int64), vp,
+                                                         C.c_size_t]),
     # a region of an image: its patch box, the post-filter on parts of images, the final crop
     ("tic_region_plan", C.c_int, [C.c_int] * 8 + [i32p] * 4),
     ("tic_rmbe_regions_device", C.c_int, [vp, vp, C.POINTER(C.c_int64)] + [C.POINTER(C.c_int32)] * 6 + [C.c_int]),

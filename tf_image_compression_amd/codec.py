@@ -71,6 +71,14 @@ class DeviceView:
             raise ValueError("array larger than the rest of the device buffer")
         check(lib().tic_memcpy_h2d(self.codec._h, self.ptr, arr.ctypes.data, arr.nbytes), "tic_memcpy_h2d")
 
+    def download(self, shape, dtype) -> np.ndarray:
+        """The bytes from this view's offset on, as ``DeviceBuffer.download``."""
+        out = np.empty(shape, dtype)
+        if out.nbytes > self.nbytes:
+            raise ValueError("requested more bytes than the rest of the device buffer holds")
+        check(lib().tic_memcpy_d2h(self.codec._h, out.ctypes.data, self.ptr, out.nbytes), "tic_memcpy_d2h")
+        return out
+
 
 class Codec:
     """A model_N codec on one GPU.  ``params``: TF-named float32 arrays (weights.py)."""
@@ -568,6 +576,93 @@ class Codec:
             self._h, d_blob.ptr, ptr(boff, C.c_int64), ptr(bsz, C.c_int64), ptr(scnt, C.c_int64), ptr(fst, C.c_int64),
             ptr(cnt, C.c_int64), n, d_sym.ptr, ptr(soff, C.c_int64), d_scratch.ptr,
             d_scratch.nbytes if scratch_bytes is None else int(scratch_bytes)), name)
+
+    # "TICA" streams: tables fitted to each stream and carried in its container (tic_entropy_emb.cpp).
+    # ``model`` is an ``entropy.Adaptive`` (not ``auto``); ``geometry`` defaults to ``code_shape``.
+    def _emb_model(self, model, geometry=None):
+        if getattr(model, "automatic", False):
+            raise ValueError("the device entries take one model per call: resolve Adaptive.auto() with choose_model")
+        eh, ew, c = (int(v) for v in (self.code_shape if geometry is None else geometry))
+        if not all(1 <= v <= 65535 for v in (eh, ew, c)):
+            raise ValueError(f"code geometry {eh} x {ew} x {c} must be in [1, 65535] each")
+        return model.K0(c), int(model.neighbours), int(model.nsym), eh, ew, c
+
+    def histogram_streams_nbr_device(self, d_sym: DeviceBuffer, sym_offsets, counts, model, segment: int,
+                                     d_counts: DeviceBuffer, geometry=None):
+        """Accumulate symbol ``k`` of stream ``i`` into row ``(k mod K0) * M + nb`` of the uint64
+        counts ``d_counts[n_streams, K0 * M, nsym]`` under ``model``'s rows at this ``segment``
+        (tic_histogram_streams_nbr_device)."""
+        n, (off, cnt) = self._stream_table(sym_offsets, counts)
+        K0, nb, nsym, eh, ew, c = self._emb_model(model, geometry)
+        need = 8 * n * K0 * 3 ** nb * nsym
+        if d_counts.nbytes < need:
+            raise ValueError(f"d_counts holds {d_counts.nbytes} bytes, the counts of {n} streams need {need}")
+        check(lib().tic_histogram_streams_nbr_device(self._h, d_sym.ptr, ptr(off, C.c_int64), ptr(cnt, C.c_int64), n,
+                                                     nsym, int(segment), K0, nb, eh, ew, c, d_counts.ptr),
+              "tic_histogram_streams_nbr_device")
+
+    @staticmethod
+    def entropy_emb_scratch_bytes(counts, segment: int, model, channels: int) -> int:
+        """Bytes of device scratch ``entropy_encode_emb_device`` / ``entropy_decode_emb_device`` need
+        (tic_entropy_emb_scratch_bytes); ``channels``: the code's C, which gives ``model`` its K0."""
+        n, (cnt,) = Codec._stream_table(counts)
+        out = C.c_size_t()
+        check(lib().tic_entropy_emb_scratch_bytes(ptr(cnt, C.c_int64), n, int(segment), model.widest().K0(channels),
+                                                  int(model.widest().neighbours), int(model.nsym), C.byref(out)),
+              "tic_entropy_emb_scratch_bytes")
+        return out.value
+
+    def entropy_encode_emb_device(self, d_sym: DeviceBuffer, sym_offsets, counts, segment: int, model,
+                                  d_scratch: DeviceBuffer, d_out: DeviceBuffer, d_sizes: DeviceBuffer,
+                                  scratch_bytes: int | None = None, out_cap: int | None = None,
+                                  geometry=None) -> None:
+        """``entropy_encode_device`` writing "TICA" containers under ``model``: the tables are
+        fitted to every stream on the device and written into its container
+        (tic_entropy_encode_emb_device; ``entropy.pack`` with an ``Adaptive`` is the host side)."""
+        n, (off, cnt) = self._stream_table(sym_offsets, counts)
+        if d_sizes.nbytes < 8 * n:
+            raise ValueError(f"d_sizes holds {d_sizes.nbytes} bytes, {n} streams need {8 * n}")
+        check(lib().tic_entropy_encode_emb_device(
+            self._h, d_sym.ptr, ptr(off, C.c_int64), ptr(cnt, C.c_int64), n, int(segment),
+            *self._emb_model(model, geometry), d_scratch.ptr,
+            d_scratch.nbytes if scratch_bytes is None else int(scratch_bytes), d_out.ptr,
+            d_out.nbytes if out_cap is None else int(out_cap), d_sizes.ptr), "tic_entropy_encode_emb_device")
+
+    def entropy_decode_emb_device(self, d_blob: DeviceBuffer, blob_offsets, blob_sizes, counts, model,
+                                  d_sym: DeviceBuffer, sym_offsets, d_scratch: DeviceBuffer,
+                                  scratch_bytes: int | None = None, geometry=None) -> None:
+        """``entropy_decode_device`` for "TICA" containers of one ``model`` (what their headers say:
+        ``entropy.parse_emb``); no table is needed (tic_entropy_decode_emb_device)."""
+        n, (boff, bsz, cnt, soff) = self._stream_table(blob_offsets, blob_sizes, counts, sym_offsets)
+        check(lib().tic_entropy_decode_emb_device(
+            self._h, d_blob.ptr, ptr(boff, C.c_int64), ptr(bsz, C.c_int64), ptr(cnt, C.c_int64), n,
+            *self._emb_model(model, geometry), d_sym.ptr, ptr(soff, C.c_int64), d_scratch.ptr,
+            d_scratch.nbytes if scratch_bytes is None else int(scratch_bytes)), "tic_entropy_decode_emb_device")
+
+    @staticmethod
+    def entropy_ranges_emb_scratch_bytes(firsts, counts, segment: int, model, channels: int) -> int:
+        """Bytes of device scratch ``entropy_decode_ranges_emb_device`` needs
+        (tic_entropy_ranges_emb_scratch_bytes)."""
+        n, (fst, cnt) = Codec._stream_table(firsts, counts)
+        out = C.c_size_t()
+        check(lib().tic_entropy_ranges_emb_scratch_bytes(ptr(fst, C.c_int64), ptr(cnt, C.c_int64), n, int(segment),
+                                                         model.K0(channels), int(model.neighbours), int(model.nsym),
+                                                         C.byref(out)), "tic_entropy_ranges_emb_scratch_bytes")
+        return out.value
+
+    def entropy_decode_ranges_emb_device(self, d_blob: DeviceBuffer, blob_offsets, blob_sizes, stream_counts, firsts,
+                                         counts, model, d_sym: DeviceBuffer, sym_offsets, d_scratch: DeviceBuffer,
+                                         scratch_bytes: int | None = None, geometry=None) -> None:
+        """``entropy_decode_ranges_device`` for "TICA" containers of one ``model``: only the header,
+        the table block, the length table and the payloads of a range's segments are read
+        (tic_entropy_decode_ranges_emb_device)."""
+        n, (boff, bsz, scnt, fst, cnt, soff) = self._stream_table(blob_offsets, blob_sizes, stream_counts, firsts,
+                                                                  counts, sym_offsets)
+        check(lib().tic_entropy_decode_ranges_emb_device(
+            self._h, d_blob.ptr, ptr(boff, C.c_int64), ptr(bsz, C.c_int64), ptr(scnt, C.c_int64), ptr(fst, C.c_int64),
+            ptr(cnt, C.c_int64), n, *self._emb_model(model, geometry), d_sym.ptr, ptr(soff, C.c_int64), d_scratch.ptr,
+            d_scratch.nbytes if scratch_bytes is None else int(scratch_bytes)),
+            "tic_entropy_decode_ranges_emb_device")
 
     def round_u8_device(self, d_in: DeviceBuffer, n: int, d_out: DeviceBuffer):
         check(lib().tic_round_u8_device(self._h, d_in.ptr, n, d_out.ptr), "tic_round_u8_device")

@@ -315,7 +315,7 @@ struct NbrWalk {
   }
   size_t t(size_t j) const { return 1 + (2 * (size_t)sym[j - b] >= nsym ? 1 : 0); }
   size_t row(size_t i) const {  // of symbol i; then advance() before the next
-    size_t nb = (w >= 1 && i - b >= m.C) ? t(i - m.C) : 0;
+    size_t nb = (m.neighbours >= 1 && w >= 1 && i - b >= m.C) ? t(i - m.C) : 0;
     if (m.neighbours == 2 && h >= 1 && i - b >= rowC) nb += 3 * t(i - rowC);
     return k0 * m.M + nb;
   }
@@ -826,6 +826,304 @@ int tic_rcseg_range_extent(const uint8_t* buf, size_t nbytes, size_t first, size
     return rc_fail(TIC_EINVAL, "segmented stream: truncated inside the length table");
   const int rc = check_range((size_t)n, first, count);
   if (rc) return rc;
+  const uint64_t S = (n + L - 1) / L, j0 = first / L, j1 = (first + count - 1) / L;
+  const uint8_t* lens = buf + header;
+  uint64_t off = header + 2 * S, len = 0;
+  for (uint64_t j = 0; j <= j1; ++j) {
+    const uint64_t l = (uint64_t)lens[2 * j] | (uint64_t)lens[2 * j + 1] << 8;
+    if (j < j0) off += l;
+    else len += l;
+  }
+  if (j0_out) *j0_out = (size_t)j0;
+  if (nj_out) *nj_out = (size_t)(j1 - j0 + 1);
+  if (byte_off) *byte_off = (size_t)off;
+  if (byte_len) *byte_len = (size_t)len;
+  return TIC_OK;
+}
+
+}  // extern "C"
+
+// --- "TICA" version 1: version 3's context model under tables fitted to the stream itself and
+// carried in the container (include/tic.h) ---
+namespace {
+const uint8_t kEmbMagic[4] = {'T', 'I', 'C', 'A'};
+constexpr size_t kEmbHeader = 40;
+constexpr uint32_t kEmbTotal = 4096;
+constexpr uint64_t kEmbMaxCount = 1ull << 40;
+
+struct EmbHead {
+  NbrModel m;
+  uint32_t L = 0;
+  uint64_t n = 0;
+  size_t T = 0, nsym = 0;
+  size_t header() const { return kEmbHeader + T; }  // the length table starts here
+};
+
+// The model's limits; fills m (ncum = nsym + 1, M = 3^neighbours).
+int emb_model(size_t K0, uint32_t neighbours, size_t nsym, uint32_t eh, uint32_t ew, uint32_t C, const char* what,
+              NbrModel* m) {
+  if (neighbours > 2)
+    return rc_fail(TIC_EINVAL, std::string(what) + ": neighbours " + std::to_string(neighbours) + " must be 0, 1 (W) or 2 (W and N)");
+  if (nsym < 2 || nsym > 256)
+    return rc_fail(TIC_EINVAL, std::string(what) + ": symbol count " + std::to_string(nsym) + " must be in [2, 256]");
+  if (eh < 1 || ew < 1 || C < 1 || eh > 65535 || ew > 65535 || C > 65535)
+    return rc_fail(TIC_EINVAL, std::string(what) + ": code geometry " + std::to_string(eh) + " x " + std::to_string(ew) + " x " +
+                                   std::to_string(C) + " must be in [1, 65535] each");
+  const size_t M = neighbours == 0 ? 1 : neighbours == 1 ? 3 : 9;
+  if (K0 < 1 || K0 > kCtxMaxEntries / (M * (nsym + 1)))
+    return rc_fail(TIC_EINVAL, std::string(what) + ": context count " + std::to_string(K0) + " must be in [1, " +
+                                   std::to_string(kCtxMaxEntries / (M * (nsym + 1))) + "]");
+  m->K0 = K0, m->M = M, m->ncum = nsym + 1, m->eh = eh, m->ew = ew, m->C = C, m->neighbours = neighbours;
+  return TIC_OK;
+}
+
+// Header and table block of a container (buf[0 .. 40 + T) must be present, nothing behind it is
+// read); tables, when not NULL, receives the K0*M cumulative rows.
+int emb_head(const uint8_t* buf, size_t nbytes, EmbHead* hd, int64_t* tables) {
+  if (!buf) return rc_fail(TIC_EINVAL, "null argument");
+  if (nbytes < 4 || memcmp(buf, kEmbMagic, 4) != 0)
+    return rc_fail(TIC_EINVAL, "not an embedded-table stream: magic is not \"TICA\"");
+  if (nbytes < kEmbHeader) return rc_fail(TIC_EINVAL, "embedded-table stream: shorter than its 40-byte header");
+  if (buf[4] != 1) return rc_fail(TIC_EINVAL, "embedded-table stream version " + std::to_string(buf[4]) + " is not supported");
+  if (buf[30] || buf[31]) return rc_fail(TIC_EINVAL, "embedded-table stream: reserved bytes are not zero");
+  const uint32_t nsym = buf[6] | (uint32_t)buf[7] << 8, K0 = rd32(buf + 20);
+  const uint32_t eh = buf[24] | (uint32_t)buf[25] << 8, ew = buf[26] | (uint32_t)buf[27] << 8,
+                 C = buf[28] | (uint32_t)buf[29] << 8;
+  int rc = emb_model(K0, buf[5], nsym, eh, ew, C, "embedded-table stream", &hd->m);
+  if (rc) return rc;
+  hd->L = rd32(buf + 8);
+  hd->n = rd64(buf + 12);
+  hd->nsym = nsym;
+  if (!seg_L_ok(hd->L))
+    return rc_fail(TIC_EINVAL, "segmented stream: segment length " + std::to_string(hd->L) + " must be a multiple of 4 in [4, 16384]");
+  if (hd->n == 0) return rc_fail(TIC_EINVAL, "segmented stream: no symbols");
+  const size_t K = hd->m.K0 * hd->m.M;
+  hd->T = K * (nsym - 1) * 2;
+  if (rd32(buf + 32) != hd->T)
+    return rc_fail(TIC_EINVAL, "embedded-table stream: table block of " + std::to_string(rd32(buf + 32)) + " bytes, " +
+                                   std::to_string(hd->T) + " expected for its model");
+  if (nbytes - kEmbHeader < hd->T) return rc_fail(TIC_EINVAL, "embedded-table stream: truncated inside the table block");
+  const uint8_t* tb = buf + kEmbHeader;
+  if (rd32(buf + 36) != tic_crc32c(tb, hd->T, 0))
+    return rc_fail(TIC_EINVAL, "embedded-table stream: the table block's CRC-32C differs from the header's");
+  for (size_t r = 0; r < K; ++r) {
+    uint32_t sum = 0;
+    if (tables) tables[r * (nsym + 1)] = 0;
+    for (size_t s = 0; s + 1 < nsym; ++s) {
+      const uint8_t* p = tb + (r * (nsym - 1) + s) * 2;
+      const uint32_t f = p[0] | (uint32_t)p[1] << 8;
+      if (f == 0)
+        return rc_fail(TIC_EINVAL, "embedded-table stream: row " + std::to_string(r) + " has a zero frequency");
+      sum += f;
+      if (sum >= kEmbTotal)
+        return rc_fail(TIC_EINVAL, "embedded-table stream: row " + std::to_string(r) + " sums to more than 4095");
+      if (tables) tables[r * (nsym + 1) + s + 1] = sum;
+    }
+    if (tables) tables[r * (nsym + 1) + nsym] = kEmbTotal;
+  }
+  return TIC_OK;
+}
+
+int emb_count(const uint8_t* sym, size_t n, uint32_t L, const NbrModel& m, uint64_t* counts) {
+  const size_t nsym = m.ncum - 1;
+  memset(counts, 0, m.K0 * m.M * nsym * sizeof(uint64_t));
+  for (size_t i = 0; i < n; ++i)  // before any row is derived from a symbol
+    if (sym[i] >= nsym) return rc_fail(TIC_EINVAL, "symbol " + std::to_string(sym[i]) + " outside the table (cumFreq too short)");
+  for (size_t b = 0; b < n; b += L) {
+    const size_t e = std::min(n, b + L);
+    NbrWalk walk(m, sym + b, b);
+    for (size_t i = b; i < e; ++i) {
+      ++counts[walk.row(i) * nsym + sym[i]];
+      walk.advance();
+    }
+  }
+  return TIC_OK;
+}
+
+// One row of the fit rule (include/tic.h): frequencies f[0 .. nsym) summing to 4096, each >= 1.
+int emb_fit_row(const uint64_t* c, size_t nsym, uint32_t* f) {
+  uint64_t nr = 0;
+  for (size_t s = 0; s < nsym; ++s) {
+    if (c[s] > kEmbMaxCount) return rc_fail(TIC_EINVAL, "a count above 2^40");
+    nr += c[s];
+  }
+  if (nr == 0) {
+    for (size_t s = 0; s < nsym; ++s) f[s] = (uint32_t)(kEmbTotal * (s + 1) / nsym - kEmbTotal * s / nsym);
+    return TIC_OK;
+  }
+  uint32_t sum = 0;
+  size_t best = 0;
+  for (size_t s = 0; s < nsym; ++s) {
+    f[s] = 1 + (uint32_t)(c[s] * (uint64_t)(kEmbTotal - nsym) / nr);
+    sum += f[s];
+    if (c[s] > c[best]) best = s;
+  }
+  f[best] += kEmbTotal - sum;
+  return TIC_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int tic_rcseg_count_nbr(const uint8_t* sym, size_t n, uint32_t L, size_t K0, uint32_t neighbours, size_t nsym,
+                        uint32_t eh, uint32_t ew, uint32_t C, uint64_t* counts) {
+  if (!sym || !counts) return rc_fail(TIC_EINVAL, "null argument");
+  if (!seg_L_ok(L)) return rc_fail(TIC_EINVAL, "segment length " + std::to_string(L) + " must be a multiple of 4 in [4, 16384]");
+  NbrModel m;
+  const int rc = emb_model(K0, neighbours, nsym, eh, ew, C, "context model", &m);
+  if (rc) return rc;
+  return emb_count(sym, n, L, m, counts);
+}
+
+int tic_rcseg_fit_tables(const uint64_t* counts, size_t K, size_t nsym, int64_t* tables) {
+  if (!counts || !tables) return rc_fail(TIC_EINVAL, "null argument");
+  if (nsym < 2 || nsym > 256) return rc_fail(TIC_EINVAL, "symbol count " + std::to_string(nsym) + " must be in [2, 256]");
+  if (K < 1 || K > kCtxMaxEntries / (nsym + 1))
+    return rc_fail(TIC_EINVAL, "row count " + std::to_string(K) + " must be in [1, " + std::to_string(kCtxMaxEntries / (nsym + 1)) + "]");
+  uint32_t f[256];
+  for (size_t r = 0; r < K; ++r) {
+    const int rc = emb_fit_row(counts + r * nsym, nsym, f);
+    if (rc) return rc;
+    int64_t* row = tables + r * (nsym + 1);
+    row[0] = 0;
+    for (size_t s = 0; s < nsym; ++s) row[s + 1] = row[s] + f[s];
+  }
+  return TIC_OK;
+}
+
+int tic_rcseg_bound_emb(size_t n, uint32_t L, size_t K0, uint32_t neighbours, size_t nsym, size_t* bytes) {
+  int rc = tic_rcseg_bound(n, L, bytes);
+  if (rc) return rc;
+  NbrModel m;
+  if ((rc = emb_model(K0, neighbours, nsym, 1, 1, 1, "context model", &m))) {
+    *bytes = 0;
+    return rc;
+  }
+  *bytes += kEmbHeader - kSegHeader + m.K0 * m.M * (nsym - 1) * 2;
+  return TIC_OK;
+}
+
+int tic_rcseg_encode_emb(const uint8_t* sym, size_t n, uint32_t L, size_t K0, uint32_t neighbours, size_t nsym,
+                         uint32_t eh, uint32_t ew, uint32_t C, uint8_t* out, size_t cap, size_t* written) {
+  if (!sym || !out || !written) return rc_fail(TIC_EINVAL, "null argument");
+  *written = 0;
+  size_t bound = 0;
+  int rc = tic_rcseg_bound_emb(n, L, K0, neighbours, nsym, &bound);
+  if (rc) return rc;
+  NbrModel m;
+  if ((rc = emb_model(K0, neighbours, nsym, eh, ew, C, "context model", &m))) return rc;
+  if (cap < bound)
+    return rc_fail(TIC_EINVAL, "output of " + std::to_string(cap) + " bytes is below tic_rcseg_bound_emb (" + std::to_string(bound) + ")");
+  const size_t K = m.K0 * m.M, ncum = m.ncum, T = K * (nsym - 1) * 2, S = (n + L - 1) / L;
+  std::vector<uint64_t> counts(K * nsym);
+  if ((rc = emb_count(sym, n, L, m, counts.data()))) return rc;
+  std::vector<int64_t> tables(K * ncum);
+  if ((rc = tic_rcseg_fit_tables(counts.data(), K, nsym, tables.data()))) return rc;
+  memcpy(out, kEmbMagic, 4);
+  out[4] = 1;
+  out[5] = (uint8_t)neighbours;
+  out[6] = (uint8_t)(nsym & 0xFF), out[7] = (uint8_t)(nsym >> 8);
+  wr32(out + 8, L);
+  wr32(out + 12, (uint32_t)((uint64_t)n & 0xFFFFFFFFu));
+  wr32(out + 16, (uint32_t)((uint64_t)n >> 32));
+  wr32(out + 20, (uint32_t)K0);
+  wr32(out + 24, eh | ew << 16);
+  wr32(out + 28, C);  // bytes 30, 31 stay zero
+  wr32(out + 32, (uint32_t)T);
+  uint8_t* tb = out + kEmbHeader;
+  for (size_t r = 0; r < K; ++r)
+    for (size_t s = 0; s + 1 < nsym; ++s) {
+      const uint32_t f = (uint32_t)(tables[r * ncum + s + 1] - tables[r * ncum + s]);
+      tb[(r * (nsym - 1) + s) * 2] = (uint8_t)(f & 0xFF);
+      tb[(r * (nsym - 1) + s) * 2 + 1] = (uint8_t)(f >> 8);
+    }
+  wr32(out + 36, tic_crc32c(tb, T, 0));
+  uint8_t* lens = tb + T;
+  uint8_t* p = lens + 2 * S;
+  for (size_t j = 0; j < S; ++j) {
+    const size_t b = j * L, e = std::min(n, b + L);
+    EncCore<MemSink> c;
+    c.s.p = p;
+    NbrWalk walk(m, sym + b, b);
+    for (size_t i = b; i < e; ++i) {
+      const size_t s = sym[i];
+      const int64_t* cum = tables.data() + walk.row(i) * ncum;
+      c.symbol((uint64_t)cum[s], (uint64_t)(cum[s + 1] - cum[s]), kEmbTotal, cum[s + 1] == kEmbTotal);
+      walk.advance();
+    }
+    c.finish();
+    const size_t len = (size_t)(c.s.p - p);
+    lens[2 * j] = (uint8_t)(len & 0xFF);
+    lens[2 * j + 1] = (uint8_t)(len >> 8);
+    p = c.s.p;
+  }
+  *written = (size_t)(p - out);
+  return TIC_OK;
+}
+
+int tic_rcseg_parse_emb(const uint8_t* buf, size_t nbytes, uint32_t* L_out, uint64_t* n_out, uint32_t* K0_out,
+                        uint32_t* eh_out, uint32_t* ew_out, uint32_t* C_out, uint32_t* neighbours_out,
+                        uint32_t* nsym_out, int64_t* tables) {
+  EmbHead hd;
+  int rc = emb_head(buf, nbytes, &hd, nullptr);
+  if (rc) return rc;
+  if ((rc = parse_framing(buf, nbytes, hd.header(), nullptr, nullptr))) return rc;
+  if (tables) (void)emb_head(buf, nbytes, &hd, tables);  // outputs only once the whole container is valid
+  if (L_out) *L_out = hd.L;
+  if (n_out) *n_out = hd.n;
+  if (K0_out) *K0_out = (uint32_t)hd.m.K0;
+  if (eh_out) *eh_out = hd.m.eh;
+  if (ew_out) *ew_out = hd.m.ew;
+  if (C_out) *C_out = hd.m.C;
+  if (neighbours_out) *neighbours_out = hd.m.neighbours;
+  if (nsym_out) *nsym_out = (uint32_t)hd.nsym;
+  return TIC_OK;
+}
+
+int tic_rcseg_decode_range_emb(const uint8_t* buf, size_t nbytes, uint8_t* sym_out, size_t n, size_t first,
+                               size_t count) {
+  if (!sym_out) return rc_fail(TIC_EINVAL, "null argument");
+  EmbHead hd;
+  int rc = emb_head(buf, nbytes, &hd, nullptr);
+  if (rc) return rc;
+  if ((rc = parse_framing(buf, nbytes, hd.header(), nullptr, nullptr))) return rc;
+  if (hd.n != (uint64_t)n)
+    return rc_fail(TIC_EINVAL, "segmented stream holds " + std::to_string(hd.n) + " symbols, " + std::to_string(n) + " expected");
+  if ((rc = check_range(n, first, count))) return rc;
+  const NbrModel& m = hd.m;
+  std::vector<int64_t> tables(m.K0 * m.M * m.ncum);
+  (void)emb_head(buf, nbytes, &hd, tables.data());
+  RangeWalk rw(buf, hd.header(), n, hd.L, first, count, sym_out);
+  for (; rw.more(); rw.next()) {
+    DecCore<MemSource> c;
+    c.s.p = rw.p;
+    c.s.end = rw.p + rw.len;
+    c.start();
+    uint8_t* seg = rw.begin();
+    NbrWalk walk(m, seg, rw.b);
+    for (size_t i = rw.b; i < rw.e; ++i) {
+      seg[i - rw.b] = (uint8_t)c.symbol(tables.data() + walk.row(i) * m.ncum, (int64_t)m.ncum - 1, kEmbTotal);
+      walk.advance();
+    }
+    rw.commit();
+  }
+  return TIC_OK;
+}
+
+int tic_rcseg_decode_emb(const uint8_t* buf, size_t nbytes, uint8_t* sym_out, size_t n) {
+  return tic_rcseg_decode_range_emb(buf, nbytes, sym_out, n, 0, n);
+}
+
+int tic_rcseg_range_extent_emb(const uint8_t* buf, size_t nbytes, size_t first, size_t count, size_t* j0_out,
+                               size_t* nj_out, size_t* byte_off, size_t* byte_len) {
+  EmbHead hd;
+  int rc = emb_head(buf, nbytes, &hd, nullptr);
+  if (rc) return rc;
+  const size_t header = hd.header();
+  const uint64_t n = hd.n, L = hd.L;
+  if (n > (UINT64_MAX >> 3) || (n + L - 1) / L > (nbytes - header) / 2)
+    return rc_fail(TIC_EINVAL, "segmented stream: truncated inside the length table");
+  if ((rc = check_range((size_t)n, first, count))) return rc;
   const uint64_t S = (n + L - 1) / L, j0 = first / L, j1 = (first + count - 1) / L;
   const uint8_t* lens = buf + header;
   uint64_t off = header + 2 * S, len = 0;

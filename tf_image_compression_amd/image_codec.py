@@ -338,13 +338,66 @@ class ImageCodec:
         encode(d_sym, offs, counts, segment, d_scr, d_blob, d_sizes)
         return d_blob, d_sizes
 
+    def _emb_models(self, d_sym: DeviceBuffer, offs, counts, model, segment: int):
+        """The ``entropy.Adaptive`` of every stream, with the codec's symbol count: ``model`` itself
+        or, under ``Adaptive.auto()``, ``entropy.choose_model`` on the stream's counts under
+        (channel, 2): one per-stream histogram on the device and one download of 9 * C * nsym
+        uint64 per stream."""
+        import dataclasses
+        from . import entropy
+        c = self.codec
+        model = dataclasses.replace(model, nsym=int(c.quan_scale))
+        if not model.automatic:
+            return [model] * len(counts)
+        ch = int(c.code_shape[2])
+        shape = (len(counts), 9 * ch, model.nsym)
+        nbytes = 8 * int(np.prod(shape))
+        d_cnt = self._buf("entropy_emb_counts", nbytes)
+        c.memset_device(d_cnt, 0, nbytes)
+        c.histogram_streams_nbr_device(d_sym, offs, counts, model.widest(), segment, d_cnt)
+        full = d_cnt.download(shape, np.uint64)
+        return [entropy.choose_model(full[i], counts[i], ch) for i in range(len(counts))]
+
+    def _entropy_encode_emb(self, d_sym: DeviceBuffer, counts, model, segment: int):
+        """``_entropy_encode`` under an ``entropy.Adaptive``: "TICA" containers, the streams grouped
+        by their model, one coder call per group.  ``(d_blob, d_sizes, order, bases)``: the sizes
+        and the containers lie in the order ``order`` of stream indices, group after group, the
+        containers of a group back to back from byte ``bases[g]`` of ``d_blob``; ``bases`` is
+        ``[(first position in order, byte offset)]``."""
+        from . import entropy
+        c = self.codec
+        geo = tuple(int(v) for v in c.code_shape)
+        offs = np.concatenate([[0], np.cumsum(counts)[:-1]]).astype(np.int64)
+        models = self._emb_models(d_sym, offs, counts, model, segment)
+        groups: dict = {}
+        for i, m in enumerate(models):
+            groups.setdefault(m, []).append(i)
+        caps = {m: sum(entropy.bound(counts[i], segment, m, geo) for i in idx) for m, idx in groups.items()}
+        need = max(c.entropy_emb_scratch_bytes([counts[i] for i in idx], segment, m, geo[2]) for m, idx in groups.items())
+        d_scr = self._buf("entropy_scratch", need)
+        d_blob = self._buf("entropy_blob", sum(-(-v // 16) * 16 for v in caps.values()))
+        d_sizes = self._buf("entropy_sizes", 8 * len(counts))
+        order, bases, at = [], [], 0
+        for m, idx in groups.items():
+            c.entropy_encode_emb_device(d_sym, offs[idx], [counts[i] for i in idx], segment, m, d_scr, d_blob.view(at),
+                                        d_sizes.view(8 * len(order)), out_cap=caps[m])
+            bases.append((len(order), at))
+            order += idx
+            at += -(-caps[m] // 16) * 16
+        self.last_models = models
+        return d_blob, d_sizes, order, bases
+
     def encode_images_to_streams(self, images, cum_freq, segment: int = 2048) -> list[bytes]:
         """[uint8 [H_i, W_i, 3]] -> one segmented-stream container per image (entropy.unpack gives
         ``encode_images``' symbols back): one upload, ``encode_images_device``, one coder call over
         all images, one download of the sizes and one of the containers.  A 2-D ``cum_freq``
         ([K, ncum]) codes symbol k of an image under row k mod K and writes version-2 containers; a
         3-D one ([K0, M, ncum]) also conditions on the causal neighbours' classes (version 3, the
-        geometry being this codec's code shape)."""
+        geometry being this codec's code shape).  An ``entropy.Adaptive`` in place of the table
+        writes "TICA" containers: the tables are fitted to every image's own symbols on the device
+        and travel inside its container (``Adaptive.auto()`` chooses the model per image;
+        ``last_models`` holds the choices)."""
+        from . import entropy
         imgs = [np.ascontiguousarray(im) for im in images]
         for im in imgs:
             if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3 or im.size == 0:
@@ -359,6 +412,20 @@ class ImageCodec:
         d_img.upload(np.concatenate([im.reshape(-1) for im in imgs]))
         d_sym = self._buf("symbols", sum(counts))
         self.encode_images_device(d_img, offsets, sizes, d_sym)
+        if isinstance(cum_freq, entropy.Adaptive):
+            d_blob, d_sizes, order, bases = self._entropy_encode_emb(d_sym, counts, cum_freq, segment)
+            nbytes = d_sizes.download((len(imgs),), np.uint64)
+            bad = np.flatnonzero(nbytes == np.iinfo(np.uint64).max)
+            if bad.size:
+                raise ValueError(f"image {order[int(bad[0])]}: a symbol outside the model's symbol count")
+            out: list = [None] * len(imgs)
+            ends = [b[0] for b in bases[1:]] + [len(order)]
+            for (k0, at), k1 in zip(bases, ends):
+                sz = nbytes[k0:k1].astype(np.int64)
+                part = d_blob.view(at).download((int(sz.sum()),), np.uint8)
+                for i, piece in zip(order[k0:k1], np.split(part, np.cumsum(sz)[:-1])):
+                    out[i] = piece.tobytes()
+            return out
         d_blob, d_sizes = self._entropy_encode(d_sym, counts, cum_freq, segment)
         nbytes = d_sizes.download((len(imgs),), np.uint64)
         bad = np.flatnonzero(nbytes == np.iinfo(np.uint64).max)
@@ -410,12 +477,85 @@ class ImageCodec:
             min_L = min(min_L, L)
         return (3 if nbr else 2 if ctx else 1), (tables if ctx or nbr else None), sizes, counts, min_L
 
+    def _check_streams_emb(self, streams, sizes, cum_freq):
+        """``_check_streams`` for "TICA" containers, which carry their tables: every container
+        parsed (entropy.parse_emb), its geometry against the codec's code shape, its symbol count
+        against the image size.  ``(models, sizes, counts, Ls)``, or None when no stream is a
+        "TICA" container and a table was given (the "TICS" path).  A list that mixes the two
+        kinds is a ValueError, as is a "TICS" stream without a table."""
+        from . import entropy
+        emb = [entropy.is_adaptive(b) for b in streams]
+        if not any(emb) and not (cum_freq is None or isinstance(cum_freq, entropy.Adaptive)):
+            return None
+        if not all(emb):
+            if any(emb):
+                raise ValueError("the list mixes \"TICA\" and \"TICS\" streams: decode them in separate calls")
+            if len(streams):
+                raise ValueError("\"TICS\" streams need the table they were coded under (cum_freq is None)")
+        sizes = [(int(H), int(W)) for H, W in sizes]
+        if len(streams) != len(sizes):
+            raise ValueError(f"{len(streams)} streams for {len(sizes)} image sizes")
+        geo = tuple(int(v) for v in self.codec.code_shape)
+        code = int(np.prod(geo))
+        models, counts, Ls = [], [], []
+        for i, (buf, (H, W)) in enumerate(zip(streams, sizes)):
+            if H <= 0 or W <= 0:
+                raise ValueError(f"image size {H}x{W} must be positive")
+            p = entropy.parse_emb(buf)
+            if p["geometry"] != geo or p["nsym"] != int(self.codec.quan_scale) or p["K0"] not in (1, geo[2]):
+                raise ValueError(f"stream {i} was coded for the code geometry {p['geometry']}, {p['nsym']} symbols and "
+                                 f"K0 {p['K0']}; this codec has {geo}, {int(self.codec.quan_scale)} symbols and K0 1 or "
+                                 f"{geo[2]}")
+            want = self.num_patches(H, W) * code
+            if p["n"] != want:
+                raise ValueError(f"stream {i} holds {p['n']} symbols, a {H}x{W} image has {want}")
+            # K0 = 1 = C (a one-channel code) is the same rows under either name
+            models.append(entropy.Adaptive("channel" if p["K0"] == geo[2] else "none", p["neighbours"], p["nsym"]))
+            counts.append(p["n"])
+            Ls.append(p["L"])
+        return models, sizes, counts, Ls
+
+    @staticmethod
+    def _groups(models):
+        groups: dict = {}
+        for i, m in enumerate(models):
+            groups.setdefault(m, []).append(i)
+        return groups
+
     def decode_streams_to_images(self, streams, sizes, cum_freq, post_filter: bool = True) -> list[np.ndarray]:
         """[container], [(H_i, W_i)] -> [uint8 [H_i, W_i, 3]]: every container is validated on the
         host (entropy.parse) and its symbol count checked against the image size and the code
         shape; then one upload, one decoder call for all of them and ``decode_images_device``.  A 2-D
         ``cum_freq`` reads version-2 containers, which must have been coded under these tables; a
-        3-D one version-3 containers coded under these tables for this codec's code shape."""
+        3-D one version-3 containers coded under these tables for this codec's code shape.  "TICA"
+        containers carry their tables: ``cum_freq`` is None (or ignored), and the streams are
+        decoded grouped by the model in their headers, one decoder call per group."""
+        emb = self._check_streams_emb(streams, sizes, cum_freq)
+        if emb is not None:
+            models, sizes, counts, Ls = emb
+            if not sizes:
+                return []
+            c = self.codec
+            blob = np.frombuffer(b"".join(bytes(b) for b in streams), np.uint8)
+            bsizes = np.array([len(b) for b in streams], np.int64)
+            boffs = np.concatenate([[0], np.cumsum(bsizes)[:-1]]).astype(np.int64)
+            soffs = np.concatenate([[0], np.cumsum(counts)[:-1]]).astype(np.int64)
+            cnts = np.array(counts, np.int64)
+            groups = self._groups(models)
+            d_blob = self._buf("entropy_blob", blob.size)
+            d_blob.upload(blob)
+            d_scr = self._buf("entropy_scratch", max(
+                c.entropy_emb_scratch_bytes(cnts[idx], min(Ls[i] for i in idx), m, c.code_shape[2])
+                for m, idx in groups.items()))
+            d_sym = self._buf("symbols", sum(counts))
+            for m, idx in groups.items():
+                c.entropy_decode_emb_device(d_blob, boffs[idx], bsizes[idx], cnts[idx], m, d_sym, soffs[idx], d_scr)
+            offsets, total = self.packed_offsets(sizes)
+            d_out = self._buf("image_out", total)
+            self.decode_images_device(d_sym, offsets, sizes, d_out, post_filter)
+            self.synchronize()
+            flat = d_out.download((total,), np.uint8)
+            return [flat[o:o + H * W * 3].reshape(H, W, 3).copy() for o, (H, W) in zip(offsets, sizes)]
         ver, tables, sizes, counts, min_L = self._check_streams(streams, sizes, cum_freq)
         if not sizes:
             return []
@@ -482,9 +622,16 @@ class ImageCodec:
         their container offsets; the rest of the device buffer is left as it was.  Then one range
         decoder call, one decoder call, one stitch, the region post-filter on the post-filter's
         stream, one rounding, the crops and one download.  ``last_region_stats`` holds, per
-        stream, the patches decoded and the bytes uploaded."""
+        stream, the patches decoded and the bytes uploaded.  "TICA" containers (``cum_freq`` None)
+        work the same way: their head also holds the table block, and the ranges are decoded
+        grouped by their container's model."""
         from . import entropy
-        ver, tables, sizes, counts, min_L = self._check_streams(streams, sizes, cum_freq)
+        emb = self._check_streams_emb(streams, sizes, cum_freq)
+        if emb is not None:  # "TICA": the tables travel in the head of every container
+            models, sizes, counts, Ls = emb
+            ver, tables, min_L = 0, None, min(Ls, default=16384)
+        else:
+            ver, tables, sizes, counts, min_L = self._check_streams(streams, sizes, cum_freq)
         if len(regions) != len(sizes):
             raise ValueError(f"{len(regions)} regions for {len(sizes)} images")
         if not sizes:
@@ -493,7 +640,8 @@ class ImageCodec:
         P = c.patch_size
         code = int(np.prod(c.code_shape))
         use_post = post_filter and self.post is not None
-        hdr = {1: entropy.HEADER_BYTES, 2: entropy.HEADER_BYTES_CTX, 3: entropy.HEADER_BYTES_NBR}[ver]
+        hdr = {0: 0, 1: entropy.HEADER_BYTES, 2: entropy.HEADER_BYTES_CTX, 3: entropy.HEADER_BYTES_NBR}[ver]
+        extent = entropy.range_extent_emb if ver == 0 else entropy.range_extent
         regions = [tuple(int(v) for v in r) for r in regions]
         bsizes = [len(b) for b in streams]
         boffs = np.concatenate([[0], np.cumsum(bsizes)[:-1]]).astype(np.int64)
@@ -504,12 +652,14 @@ class ImageCodec:
             py0, py1, px0, px1 = self.region_plan((H, W), (y, x, h, w), post_filter)
             wn = self.grid(H, W)[1]
             L = int.from_bytes(bytes(buf[8:12]), "little")  # validated above
+            if ver == 0:  # header, table block, length table
+                hdr = entropy.HEADER_BYTES_EMB + int.from_bytes(bytes(buf[32:36]), "little")
             head = bytes(buf[:hdr + 2 * -(-counts[i] // L)])
             extents = []
             for py in range(py0, py1):
                 first, count = (py * wn + px0) * code, (px1 - px0) * code
                 r_stream.append(i), r_first.append(first), r_count.append(count)
-                extents.append(entropy.range_extent(head, first, count)[2:])
+                extents.append(extent(head, first, count)[2:])
             merged = self._merge_extents(extents)
             pieces += [(int(boffs[i]), head)] + [(int(boffs[i]) + o, bytes(buf[o:o + ln])) for o, ln in merged]
             boxes.append((min(py1 * P, H) - py0 * P, min(px1 * P, W) - px0 * P))
@@ -523,17 +673,29 @@ class ImageCodec:
             c.entropy_set_tables_nbr(tables)
         elif ver == 2:
             c.entropy_set_tables(tables)
-        else:
+        elif ver == 1:
             c.entropy_set_table(cum_freq)
         d_blob = self._buf("entropy_blob", int(sum(bsizes)))
         for at, data in pieces:  # the sparse upload: everything else in d_blob stays as it was
             d_blob.view(at).upload(np.frombuffer(data, np.uint8))
-        d_scr = self._buf("entropy_scratch", c.entropy_ranges_scratch_bytes(r_first, r_count, min_L))
         d_sym = self._buf("symbols", n_box * code)
         soffs = np.concatenate([[0], np.cumsum(r_count)[:-1]]).astype(np.int64)
-        c.entropy_decode_ranges_device(d_blob, [boffs[i] for i in r_stream], [bsizes[i] for i in r_stream],
-                                       [counts[i] for i in r_stream], r_first, r_count, d_sym, soffs, d_scr,
-                                       version=ver)
+        if ver == 0:  # the ranges grouped by their container's model, one range-decoder call per group
+            groups = self._groups([models[i] for i in r_stream])
+            pick = lambda vals, idx: [vals[k] for k in idx]
+            d_scr = self._buf("entropy_scratch", max(
+                c.entropy_ranges_emb_scratch_bytes(pick(r_first, idx), pick(r_count, idx), min_L, m, c.code_shape[2])
+                for m, idx in groups.items()))
+            for m, idx in groups.items():
+                rs = pick(r_stream, idx)
+                c.entropy_decode_ranges_emb_device(d_blob, [boffs[i] for i in rs], [bsizes[i] for i in rs],
+                                                   [counts[i] for i in rs], pick(r_first, idx), pick(r_count, idx), m,
+                                                   d_sym, soffs[idx], d_scr)
+        else:
+            d_scr = self._buf("entropy_scratch", c.entropy_ranges_scratch_bytes(r_first, r_count, min_L))
+            c.entropy_decode_ranges_device(d_blob, [boffs[i] for i in r_stream], [bsizes[i] for i in r_stream],
+                                           [counts[i] for i in r_stream], r_first, r_count, d_sym, soffs, d_scr,
+                                           version=ver)
         # the boxes are the images of a group: decode_images_device's steps with the region filter
         offsets, total = self.packed_offsets(boxes)
         runs = self._runs(offsets, boxes)
@@ -592,12 +754,19 @@ class ImageCodec:
         (tic_histogram_ctx_device) and ``coded_bytes`` the size of its version-2 container; under a
         3-D one ([K0, M, Q + 1]) ``est_bits`` uses the rows the neighbour coder uses at
         ``entropy_segment`` (tic_histogram_nbr_device; entropy.DEFAULT_SEGMENT without one) and
-        ``coded_bytes`` is the size of the version-3 container.  Images
+        ``coded_bytes`` is the size of the version-3 container.  Under an ``entropy.Adaptive``
+        ``coded_bytes`` is the size of the image's "TICA" container, tables included (at
+        ``entropy_segment``, entropy.DEFAULT_SEGMENT without one), and ``est_bits`` is None: the
+        tables are the image's own.  Images
         start at 4-byte boundaries of the arena (the alignment tic_sse_u8_device asks for)."""
         from . import entropy
         from . import evaluate as ev
-        tables = entropy.ctx_tables(cum_freq) if cum_freq is not None and entropy.is_ctx_table(cum_freq) else None
-        nbr = cum_freq is not None and entropy.is_nbr_table(cum_freq)
+        adaptive = isinstance(cum_freq, entropy.Adaptive)  # real coded_bytes, no estimate: the tables are the image's own
+        if adaptive and entropy_segment is None:
+            entropy_segment = entropy.DEFAULT_SEGMENT
+        tables = entropy.ctx_tables(cum_freq) if cum_freq is not None and not adaptive and entropy.is_ctx_table(cum_freq) \
+            else None
+        nbr = cum_freq is not None and not adaptive and entropy.is_nbr_table(cum_freq)
         if nbr:  # the estimate sees the K0 * M rows as a version-2 estimate sees its K rows
             t3 = entropy.nbr_tables(cum_freq)
             tables = t3.reshape(-1, t3.shape[2])
@@ -628,7 +797,11 @@ class ImageCodec:
         d_out = self._buf("image_out", total)
         self.encode_images_device(d_img, offsets, sizes, d_sym)
         d_sizes = None
-        if entropy_segment is not None and cum_freq is not None:
+        emb_order = None
+        if adaptive:
+            _, d_sizes, emb_order, _ = self._entropy_encode_emb(d_sym, [k * code for k in counts], cum_freq,
+                                                                int(entropy_segment))
+        elif entropy_segment is not None and cum_freq is not None:
             _, d_sizes = self._entropy_encode(d_sym, [k * code for k in counts], cum_freq, int(entropy_segment))
         self.decode_images_device(d_sym, offsets, sizes, d_out, post_filter)
         if post_filter and self.post is not None:
@@ -667,6 +840,8 @@ class ImageCodec:
         sums = raw[n * rec:].view(np.float64).reshape(len(big), 5, 3, 2)
         ms = {i: ev.msssim_from_sums(sums[k], *sizes[i]) for k, i in enumerate(big)}
         coded = None if d_sizes is None else d_sizes.download((n,), np.uint64)
+        if emb_order is not None:  # the sizes lie group after group
+            coded = coded[np.argsort(emb_order)]
         if coded is not None and np.any(coded == np.iinfo(np.uint64).max):
             raise ValueError("a symbol outside the frequency table")
         out = []
@@ -675,7 +850,7 @@ class ImageCodec:
             cnt = ints[i, 1:].copy()
             with np.errstate(divide="ignore"):
                 psnr = float(ev.mse2psnr(np.float64(sse) / (H * W * 3)))
-            if cum_freq is None:
+            if cum_freq is None or adaptive:
                 est = None
             elif tables is not None:
                 est = ev.estimated_bits_ctx(ctx_counts[i], tables)
